@@ -16,6 +16,30 @@ One step = one wave of ``--convs`` concurrent turns per GPU (weak scaling: per-G
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --steps 3 --warmup 1
 
 ``--gpus N`` must equal the launcher's WORLD_SIZE (non-zero exit otherwise).
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.
+``--full`` is where measurements beyond the headline figure belong (none exist today: every figure
+of the result line comes out of the timed steps themselves), so that the plain run stays lean.
+
+The inputs are the same from run to run: weights, corpus and conversations are seeded, the clock
+the data see is pinned (``BENCH_EPOCH``), and every sampling seed derives from its prompt.
+``--dump-outputs DIR`` writes what the last timed step handed its callers (rank 0's replica; the
+leader of any other replica adds ``_rank<r>`` to the names):
+
+    DIR/decide_token_ids.npy    float32 [convs, 160]: the decide call's output in each
+                                conversation's last timed turn, in conversation order (the tool
+                                call or "No tool call"; -1 = padding)
+    DIR/retrieval_scores.npy    float32 [convs, 32]: the best 32 hit scores the retrieval tool
+                                returned in that turn (0 = no hit / the turn did not retrieve)
+    DIR/respond_lengths.npy     float32 [convs]: the number of reply tokens streamed in that turn
+
+These are functions of the inputs alone and repeat exactly from run to run.  The reply tokens
+themselves are left out because on the GPU they are not: they are sampled (temperature 0.5) from
+bf16 logits of random weights, the make-up of each batch follows the closed loop's timing, and one
+rounding difference that flips a token changes the rest of that reply and, through the history,
+every later turn of its conversation.  Two GPU runs of one build agree on 98 % of the replies'
+first tokens in a one-step run, lose about 3 % per position after that and share no reply token
+after a few turns, so an array of them would say nothing about a build.
 """
 from __future__ import annotations
 
@@ -32,6 +56,12 @@ METRIC = "chat turns/sec + p50 TTFT, Llama-3-8B RAG agent at 1/2/4/8 MI355X"
 
 MODEL_LABELS = {"llama3-8b": "Llama-3-8B", "llama3.1-8b": "Llama-3.1-8B", "llama3-70b": "Llama-3-70B",
                 "mixtral-8x7b": "Mixtral-8x7B"}
+
+# the "now" of the synthetic data: corpus dates count back from it, "the last N days" filters and
+# the prompts' current date are taken at it, so a run's inputs do not depend on when it starts
+BENCH_EPOCH = 1_750_000_000
+DUMP_TOP_SCORES = 32
+DUMP_DECIDE_TOKENS = 160        # LLMAgent's max_decide_tokens
 
 
 def log(msg: str) -> None:
@@ -87,7 +117,87 @@ def parse(argv=None):
                          "the step's all-reduce volume priced at stated xGMI rates -- a projection, never a "
                          "multi-GPU measurement")
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed and the inputs alone "
+                         "determine (decide tokens, retrieval scores and reply lengths per conversation, rank 0's "
+                         "replica) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that are not part of the headline figure (none today); a run "
+                         "without it only sets up, warms up, times the steps and prints the result line")
     return ap.parse_args(argv)
+
+
+def pin_inputs(engine, llm, retrieval, agent) -> tuple:
+    """Make the run's inputs a function of the arguments alone, and keep what each turn's callers
+    receive.  Sampling seeds default to a hash of the request id (salted per process): derive them
+    from the prompt instead.  Date filters and the prompts' date default to the wall clock: take
+    them at BENCH_EPOCH, where the corpus dates end.  Returns (replies, scores): the LLM calls'
+    output tokens by (purpose, turn) and the retrieval's best scores by turn, a turn
+    being named by its start time (``TURN_START``, which ``TurnTrace.t_receive`` carries too)."""
+    import datetime
+    import zlib
+    from array import array
+
+    from financial_chatbot_llm_amd.engine.sequence import TURN_START
+    replies, scores = {}, {}
+
+    generate = engine.generate
+
+    def seeded_generate(prompt_ids, params, request_id=None):
+        if params.seed is None:
+            tail = array("q", prompt_ids[-512:])
+            params.seed = zlib.crc32(tail.tobytes(), len(prompt_ids)) & 0x7FFFFFFF
+        return generate(prompt_ids, params, request_id)
+    engine.generate = seeded_generate
+
+    account = llm._account
+
+    def account_and_keep(purpose, prompt_len, seq):
+        account(purpose, prompt_len, seq)
+        if purpose in ("respond", "decide"):      # a multi-step turn keeps its last decision
+            replies[(purpose, TURN_START.get())] = list(seq.output_ids)
+    llm._account = account_and_keep
+
+    search = retrieval.search
+
+    async def search_at_epoch(query, user_id, date_gte, limit):
+        if date_gte is not None:      # "the last N days", N recovered from the wall-clock bound
+            date_gte = BENCH_EPOCH - 86400 * round((time.time() - date_gte) / 86400)
+        hits = await search(query, user_id, date_gte, limit)
+        scores[TURN_START.get()] = [h.score for h in hits[:DUMP_TOP_SCORES]]
+        return hits
+    retrieval.search = search_at_epoch
+
+    if hasattr(agent, "today_fn"):
+        today = datetime.date.fromtimestamp(BENCH_EPOCH)
+        agent.today_fn = lambda: today
+    return replies, scores
+
+
+def dump_outputs(path: str, rank: int, wl, traces, replies, scores) -> None:
+    """The outputs of each conversation's last timed turn that the inputs alone determine, as
+    float32 arrays in conversation order (the module docstring says why the sampled reply tokens
+    are not among them)."""
+    import numpy as np
+    last = {}
+    for tr in traces:
+        last[tr.conversation_id] = tr.t_receive
+    n = len(wl.convs)
+    dec = np.full((n, DUMP_DECIDE_TOKENS), -1.0, np.float32)
+    top = np.zeros((n, DUMP_TOP_SCORES), np.float32)
+    lens = np.zeros(n, np.float32)
+    for i, doc in enumerate(wl.convs):
+        key = last.get(doc["conversation_id"])
+        d = replies.get(("decide", key), [])[:DUMP_DECIDE_TOKENS]
+        dec[i, :len(d)] = d
+        lens[i] = len(replies.get(("respond", key), []))
+        s = scores.get(key, [])
+        top[i, :len(s)] = s
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    np.save(os.path.join(path, f"decide_token_ids{tag}.npy"), dec)
+    np.save(os.path.join(path, f"retrieval_scores{tag}.npy"), top)
+    np.save(os.path.join(path, f"respond_lengths{tag}.npy"), lens)
 
 
 async def run(args, ps):
@@ -156,7 +266,7 @@ async def run(args, ps):
     t0 = time.perf_counter()
     embedder = BgeEmbedder(args.embed_model, device=str(dev), seed=ps.rank)
     store = DeviceVectorStore(embedder.dim, device=str(dev))
-    store.load_synthetic(args.corpus, args.users, seed=ps.rank)
+    store.load_synthetic(args.corpus, args.users, seed=ps.rank, now=BENCH_EPOCH)
     retrieval = RetrievalService(embedder, store)
     log(f"retrieval ready ({args.corpus} vectors) in {time.perf_counter() - t0:.1f}s")
 
@@ -177,6 +287,7 @@ async def run(args, ps):
     wl = RagWorkload(llm, retrieval, args.convs, args.users, args.respond_tokens, rank=ps.rank,
                      max_tool_steps=args.tool_steps, tools=not args.no_tools)
     wl.progress = log
+    replies, scores = pin_inputs(engine, llm, retrieval, wl.agent)
     wl.kafka.setup_consumer()
     consumer = asyncio.create_task(wl.worker.consume_messages())
 
@@ -232,6 +343,8 @@ async def run(args, ps):
     await consumer
     stats = engine.stats()
     engine.shutdown()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ps.rank, wl, wl.worker.traces, replies, scores)
     turns = sum(r.turns for r in results)
     # prompt-token accounting of the timed turns (account for every prefill token)
     tokens = {}

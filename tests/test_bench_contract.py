@@ -45,12 +45,22 @@ def _check(d, n):
 
 
 @pytest.mark.timeout(300)
-def test_bench_single_process_json_contract():
-    r = subprocess.run([sys.executable, "bench.py", *ARGS], cwd=ROOT, capture_output=True, text=True, timeout=280)
+def test_bench_single_process_json_contract(tmp_path):
+    r = subprocess.run([sys.executable, "bench.py", *ARGS, "--dump-outputs", str(tmp_path / "out")], cwd=ROOT,
+                       capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
     _check(lines[0], 1)
+    # --dump-outputs: what the timed step handed its callers, one row per conversation
+    import numpy as np
+    lens = np.load(tmp_path / "out" / "respond_lengths.npy")
+    top = np.load(tmp_path / "out" / "retrieval_scores.npy")
+    assert lens.dtype == np.float32 and lens.tolist() == [4.0] * 3                  # --convs 3, --respond-tokens 4
+    dec = np.load(tmp_path / "out" / "decide_token_ids.npy")
+    assert dec.dtype == np.float32 and dec.shape[0] == 3 and (dec[:, 0] >= 0).all()    # every turn decides
+    assert top.dtype == np.float32 and top.shape[0] == 3
+    assert int((top != 0).any(axis=1).sum()) == lines[0]["retrieval_turns"]
 
 
 @pytest.mark.timeout(400)
@@ -167,9 +177,10 @@ def test_bench_tensor_parallel_replica_on_one_gpu_json_contract():
 @pytest.mark.timeout(300)
 def test_bench_tp_shard_estimate_mode():
     """``--tp-shard-estimate N``: one process runs rank 0's TP=N shard with its
-    collectives stubbed and projects the all-reduce time at stated xGMI rates."""
-    r = subprocess.run([sys.executable, "bench.py", *ARGS, "--tp-shard-estimate", "2"], cwd=ROOT, capture_output=True,
-                       text=True, timeout=280, env=_clean_env())
+    collectives stubbed and projects the all-reduce time at stated xGMI rates (the projection is
+    arithmetic on the timed steps' own counters, so ``--full`` adds nothing to it)."""
+    r = subprocess.run([sys.executable, "bench.py", *ARGS, "--tp-shard-estimate", "2", "--full"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=280, env=_clean_env())
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_lines(r.stdout)[0]
     e = d["tp_shard_estimate"]
