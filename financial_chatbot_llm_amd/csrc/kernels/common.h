@@ -103,7 +103,7 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
   return t;
 }
 
-// splitmix64 -> two uniforms in (0, 1); counter-based so results are launch-order independent.
+// splitmix64 -> 64 random bits (the low 32 feed u01_from_bits); counter-based so results are launch-order independent.
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -112,8 +112,10 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 }
 
 __device__ __forceinline__ float u01_from_bits(uint32_t b) {
-  // 24 random mantissa bits, strictly inside (0, 1)
-  return ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  // 23 random bits, strictly inside (0, 1): x + 0.5 needs 24 significant bits for x < 2^23, so
+  // every step is exact in float32 (min 2^-24, max 1 - 2^-24).  With 24 bits x + 0.5f rounds from
+  // 2^23 upwards and reaches exactly 1.0f at the top, whose Gumbel noise is +inf.
+  return ((float)(b >> 9) + 0.5f) * (1.0f / 8388608.0f);
 }
 
 // Gumbel noise of vocabulary entry idx for a row seeded `seed` (K12 and the fused LM-head sampler

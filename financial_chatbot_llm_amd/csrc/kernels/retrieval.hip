@@ -10,8 +10,8 @@
 //   2. score: one wave per candidate row computes <corpus_row, query> (768-d bf16, 16 B/lane).
 //   3. select: one workgroup per query bitonic-sorts up to SORT_CAP (score, row) pairs in LDS,
 //      descending by score, ties by row id, and writes the first k.
-// Queries with more candidates than SORT_CAP are finished by the caller (torch.topk on the
-// device-side score list), which the host detects from the returned counts.
+// Queries with more candidates than SORT_CAP are finished by the caller (ops/retrieval.py, in the
+// same order, from the device-side score list), which the host detects from the returned counts.
 #include "common.h"
 
 #define SORT_CAP 8192

@@ -30,6 +30,19 @@ def filtered_topk_ref(corpus, user_codes, dates, queries, q_user, q_floor, ks, k
     return ids, scores, counts
 
 
+def _best_first(scores: torch.Tensor, ids: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best of (score descending, row id ascending), the select kernel's order.  torch.topk
+    leaves the order of tied scores open (and the candidate list's order comes from atomics), so
+    only its k-th score is used: every candidate at or above it is ordered by the pair."""
+    if k <= 0:
+        return ids[:0], scores[:0]
+    kth = torch.topk(scores, k).values[-1]
+    sel = (scores >= kth).nonzero().flatten()
+    sel = sel[torch.argsort(ids[sel], stable=True)]
+    sel = sel[torch.sort(scores[sel], descending=True, stable=True).indices][:k]
+    return ids[sel], scores[sel]
+
+
 class _Workspace:
     def __init__(self):
         self.key = None
@@ -73,16 +86,15 @@ def filtered_topk(corpus: torch.Tensor, user_codes: torch.Tensor, dates: torch.T
            N.ptr(out_ids), N.ptr(out_scores), N.ptr(out_count), N.stream())
     oc = out_count.cpu()
     big = (oc < 0).nonzero().flatten().tolist()
-    for i in big:  # > SORT_CAP candidates: finish on device with torch.topk
+    for i in big:  # > SORT_CAP candidates: finish on device, in the select kernel's order
         total = -int(oc[i])
         k = min(int(ks[i]), total, kmax)
         if total <= cap:
-            s, j = torch.topk(scores[i, :total], k)
-            out_ids[i, :k], out_scores[i, :k] = cand[i, :total][j], s
+            out_ids[i, :k], out_scores[i, :k] = _best_first(scores[i, :total], cand[i, :total], k)
         else:
             mask = (user_codes == q_user[i]) & (dates >= q_floor[i])
             full = (corpus.float() @ queries[i].float()).masked_fill(~mask, float("-inf"))
-            s, j = torch.topk(full, k)
-            out_ids[i, :k], out_scores[i, :k] = j.to(torch.int32), s
+            rows = torch.arange(full.numel(), dtype=torch.int32, device=full.device)
+            out_ids[i, :k], out_scores[i, :k] = _best_first(full, rows, k)
         oc[i] = k
     return out_ids, out_scores, oc.to(corpus.device)

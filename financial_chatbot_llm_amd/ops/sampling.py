@@ -13,8 +13,9 @@ SPLITS = 16  # vocab slices per row in the HIP sampler (SAMPLE_SPLITS)
 
 def _aligned_rows(logits: torch.Tensor) -> torch.Tensor:
     """The HIP samplers load 16-B vectors from each row: a row stride that is not a multiple of 8
-    elements (a vocab shard of odd width, e.g. V/tp) is copied into a buffer whose stride is."""
-    if logits.stride(1) == 1 and logits.stride(0) % 8 == 0:
+    elements (a vocab shard of odd width, e.g. V/tp), or a view that starts off a 16-B boundary (a
+    column slice of wider logits), is copied into a buffer whose stride and base are aligned."""
+    if logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0:
         return logits
     B, V = logits.shape
     buf = torch.empty((B, -(-V // 8) * 8), dtype=logits.dtype, device=logits.device)
@@ -259,7 +260,8 @@ def apply_top_k_top_p(logits: torch.Tensor, top_k: torch.Tensor, top_p: torch.Te
     scaled = (sorted_l / t.clamp(min=1e-6)[:, None]).masked_fill(drop, float("-inf"))
     probs = torch.softmax(scaled, dim=-1)
     cum = probs.cumsum(-1) - probs                 # mass strictly above each token
-    drop |= cum >= top_p.float().to(lf.device)[:, None]
+    pf = top_p.float().to(lf.device)[:, None]
+    drop |= (cum >= pf) & (pf < 1)                 # p >= 1: off (the fp32 cumsum can round up to 1.0)
     drop &= (t > 0)[:, None]
     drop[:, 0] = False
     sorted_l = sorted_l.masked_fill(drop, float("-inf"))
