@@ -178,8 +178,9 @@ class MixtralModel(DecoderModel):
                                                    self.w[p + "w2_t"], self.w[p + "w2_scale"])
             return ep_moe(h, logits, c.top_k_experts, c.num_experts, lambda rows, e: self._expert(p, rows, e),
                           group=pstate().tp_group, grouped_fn=grouped)
-        # fp8 MFMA pipeline while the step is weight-bandwidth-bound; bigger prefill chunks go to
-        # hipBLASLt on the cached bf16 copy of the same quantized experts (compute-bound regime)
+        # fp8 MFMA pipeline while the step is weight-bandwidth-bound; bigger prefill chunks go to the
+        # grouped fp8 tile kernel below (compute-bound regime), or without the row-major fp8 experts
+        # to the bucketed per-expert loop at the end
         fp8_limit = 1024 if (self.prefill_dequant_cache or self.prefill_fp8) else 4096
         if self.fp8 and ops._native.use_native(h) and T * c.top_k_experts <= fp8_limit:
             out = moe_ops.moe_decode_fp8(h.contiguous(), logits.contiguous(), self.w[p + "w13_t"],
