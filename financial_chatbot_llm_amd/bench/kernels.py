@@ -568,6 +568,49 @@ def bench_lm_head_fused(dev) -> List[Dict]:
     return out
 
 
+def bench_lm_head_logprob(dev, Ms=(256, 2048, 8192)) -> List[Dict]:
+    """Prompt scoring's LM head (vocab 128256, K 4096): the tile kernel with the log-likelihood
+    epilogue (ops.lm_head_logprobs, no logits in HBM) vs the reference path on the device (logits ->
+    f32 log-softmax -> gather, PENNY_FUSED_LOGPROB=0): time and peak extra memory of one call."""
+    import os
+    from .. import ops
+    from ..ops import gemm
+    gemm.load_gemm_tuning("llama3-8b")
+    out = []
+    V, K = 128256, 4096
+    w = torch.randn((V, K), device=dev).to(torch.bfloat16) * 0.02
+
+    def peak(fn) -> float:
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        fn()
+        torch.cuda.synchronize()
+        return (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20
+
+    for M in Ms:
+        x = torch.randn((M, K), device=dev).to(torch.bfloat16)
+        tg = torch.randint(0, V, (M,), device=dev, dtype=torch.int32)
+        row = {"op": "lm_head_logprob", "M": M, "V": V, "K": K}
+        res = {}
+        for name, flag in (("fused", "1"), ("reference", "0")):
+            os.environ["PENNY_FUSED_LOGPROB"] = flag
+            try:
+                res[name] = ops.lm_head_logprobs(x, w, tg)
+                row[f"{name}_us"] = round(timeit(lambda: ops.lm_head_logprobs(x, w, tg), iters=5, rounds=3), 1)
+                row[f"{name}_peak_mib"] = round(peak(lambda: ops.lm_head_logprobs(x, w, tg)), 1)
+            finally:
+                os.environ.pop("PENNY_FUSED_LOGPROB", None)
+        row["speedup"] = round(row["reference_us"] / row["fused_us"], 3)
+        row["fused_TFLOPs"] = round(2.0 * M * V * K / row["fused_us"] / 1e6, 1)
+        row["max_abs_diff"] = float((res["fused"] - res["reference"]).abs().max())
+        out.append(row)
+        print(json.dumps(row), flush=True)
+        del res
+        torch.cuda.empty_cache()
+    return out
+
+
 def bench_bge_query(dev) -> List[Dict]:
     """bge-base encoder latency on retrieval-size query batches (the per-turn critical path): the
     four projections on hipBLASLt (+ the GELU pass) vs the tile kernel with the bias / bias+GELU
@@ -1589,7 +1632,7 @@ def main(argv=None) -> int:
     res = []
     for name in args.only.split(","):
         res += {"decode": bench_decode, "decode_mixed": bench_decode_mixed, "decode_lean": bench_decode_lean, "prefill": bench_prefill, "prefill_mixed": bench_prefill_mixed, "prefill_spec_split": bench_prefill_spec_split, "elementwise": bench_elementwise,
-                "topk": bench_topk, "gemm": bench_gemm, "gemm_prefill": bench_gemm_prefill, "lm_head": bench_lm_head, "lm_head_fused": bench_lm_head_fused, "bge_query": bench_bge_query, "gemm_tail": bench_gemm_tail,
+                "topk": bench_topk, "gemm": bench_gemm, "gemm_prefill": bench_gemm_prefill, "lm_head": bench_lm_head, "lm_head_fused": bench_lm_head_fused, "lm_head_logprob": bench_lm_head_logprob, "bge_query": bench_bge_query, "gemm_tail": bench_gemm_tail,
                 "gemm_tune": bench_gemm_tune_sweep, "skinny": bench_skinny, "splitk": bench_splitk,
                 "splitk_qkv": lambda d: bench_splitk(d, ("qkv",)), "gateup": bench_gateup, "moe": bench_moe,
                 "moe_prefill": bench_moe_prefill, "gemm_hip": bench_gemm_hip, "gemm_hip_quick": lambda d: bench_gemm_hip(d, [512, 1024, 2048, 3072, 4096]), "gemm_hip_check": check_gemm_hip, "gemm_lds_probe": gemm_lds_probe, "prefill_policy": bench_prefill_policy, "prefill_policy_quick": lambda d: bench_prefill_policy(d, [512, 1024, 1536, 2048, 2560, 3072, 3584, 4096]), "prefill_policy_70b": lambda d: bench_prefill_policy(d, [384, 512, 768, 1024, 1536, 2048, 2560, 3072, 4096], model="70b"),

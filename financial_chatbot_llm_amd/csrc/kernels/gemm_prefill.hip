@@ -15,6 +15,9 @@
 //             logit / T + Gumbel noise of (row seed, token id), sampler.hip's draw) and the
 //             workgroup leaves one (best score, token) pair per (token row, 128-column wave half);
 //             lm_sample_final_kernel reduces the V / 128 pairs of a row to the sampled token
+//   EPI_LOGPROB the LM head fused with prompt scoring (EPI_SAMPLE's sibling): per (token row, wave
+//             half) the max, sum of exp(l - max), target logit and argmax of the bf16-rounded logits;
+//             lm_logprob_final_kernel merges a row's partials to log softmax at the target token
 //   EPI_ROPE  the fused QKV projection (K3+K4+K5): a wave's 128 output columns are exactly one
 //             head, so the rotate-half RoPE pair (d, d+64) sits in one lane (accumulators f, f+4);
 //             q heads -> rotated q [M, Hq, 128]; k heads -> rotated, v heads -> as is, both
@@ -68,7 +71,8 @@ constexpr int GM = 4;                // token tiles per L2 group (r5 sweep of 1-
                                      // profiles/r5_tile_gemm_l2_group_sweep.jsonl)
 enum { H_W0 = 0, H_X0 = 1, H_X1 = 2, H_W1 = 3 };
 enum { EPI_BF16 = 0, EPI_SILU = 1, EPI_SLAB = 2, EPI_RESID = 3, EPI_ROPE = 4, EPI_BIAS = 5, EPI_BIAS_GELU = 6,
-       EPI_MOE_SILU = 7, EPI_MOE_ROUTE = 8, EPI_SAMPLE = 9, EPI_MOE_SILU_MX = 10, EPI_MOE_ROUTE_MX = 11 };
+       EPI_MOE_SILU = 7, EPI_MOE_ROUTE = 8, EPI_SAMPLE = 9, EPI_MOE_SILU_MX = 10, EPI_MOE_ROUTE_MX = 11,
+       EPI_LOGPROB = 12 };
 
 // Grouped fp8 MoE GEMM (penny_moe_gemm_prefill_fp8): rows sorted by expert, bucket bounds on the
 // DEVICE (offsets [E+1]), so tiles are found without a host round trip.
@@ -97,6 +101,18 @@ struct SampleArgs {
   const unsigned long long* seeds;
   float* pv;
   int* pi;
+  int voff, vvalid;
+};
+
+// EPI_LOGPROB: targets [M] (global token id, < 0: none); pm / ps / pt / pa [M, 2 * N / 256] partial
+// (max, sum of exp(l - max), target logit, argmax id) of each (row, wave half of 128 columns).
+// voff / vvalid as in SampleArgs.
+struct LogprobArgs {
+  const int* targets;
+  float* pm;
+  float* ps;
+  float* pt;
+  int* pa;
   int voff, vvalid;
 };
 
@@ -265,7 +281,7 @@ __global__ void __launch_bounds__(512) gemm_prefill_kernel(const void* __restric
                                                            void* __restrict__ Y, int ldy,
                                                            const bf16* __restrict__ R, int ldr,
                                                            int M, int N, int S, RopeArgs ra, MoeArgs ma,
-                                                           SampleArgs sa, TailArgs ta) {
+                                                           SampleArgs sa, TailArgs ta, LogprobArgs la) {
   static_assert(!(WT && FP8), "fragment-tiled W: bf16 only");
   constexpr int ESZ = FP8 ? 1 : 2;        // bytes per element
   constexpr int BKE = 128 / ESZ;          // elements per K-tile row (128 bytes)
@@ -724,6 +740,45 @@ __global__ void __launch_bounds__(512) gemm_prefill_kernel(const void* __restric
         sa.pv[slot] = bv;
         sa.pi[slot] = bi;
       }
+    } else if constexpr (EPI == EPI_LOGPROB) {
+      // the log-likelihood sibling of EPI_SAMPLE, same lane set per row: the wave half's max / argmax
+      // and target logit first, then its sum of exp(l - max) against the reduced max
+      const int tgt = la.targets[m];
+      const int loc0 = n0 + wa * 128 + 4 * g;
+      float bv = -INFINITY, tl = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int f = 0; f < 8; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int loc = loc0 + f * 16 + r, idx = la.voff + loc;
+          float v = (float)(bf16)acc[f][t][r];          // the bf16 logit the unfused path scores
+          if (loc >= la.vvalid) v = -INFINITY;
+          better(bv, bi, v, idx);
+          if (idx == tgt) tl = v;                       // tgt < 0 matches no column (voff >= 0)
+        }
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        better(bv, bi, ov, oi);
+        tl = fmaxf(tl, __shfl_xor(tl, o, 64));
+      }
+      float ps = 0.f;
+#pragma unroll
+      for (int f = 0; f < 8; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (loc0 + f * 16 + r < la.vvalid) ps += __expf((float)(bf16)acc[f][t][r] - bv);
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) ps += __shfl_xor(ps, o, 64);
+      if (g == 0) {
+        const long slot = (long)m * (2 * Nt) + 2 * tn + wa;
+        la.pm[slot] = bv;
+        la.ps[slot] = ps;
+        la.pt[slot] = tl;
+        la.pa[slot] = bi;
+      }
     } else if constexpr (EPI == EPI_ROPE) {
       constexpr int D = 128;
       const int hd = (n0 + wa * 128) >> 7;     // this wave's head (q heads, then k, then v)
@@ -831,7 +886,7 @@ static void launch(dim3 grid, hipStream_t stream, const void* X, int ldx, const 
                    const void* R, int ldr, int M, int N, int S, const RopeArgs& ra, TailArgs ta = TailArgs{}) {
   ta.gm = g_group;
   hipLaunchKernelGGL((gemm_prefill_kernel<EPI, ABL, BAL, false, WT>), grid, dim3(512), 0, stream, X, ldx, W, K, Y,
-                     ldy, (const bf16*)R, ldr, M, N, S, ra, MoeArgs{}, SampleArgs{}, ta);
+                     ldy, (const bf16*)R, ldr, M, N, S, ra, MoeArgs{}, SampleArgs{}, ta, LogprobArgs{});
 }
 
 static dim3 grid_for(int M, int N, int S) { return dim3((unsigned)(((M + TM - 1) / TM) * (N / TN) * S)); }
@@ -973,7 +1028,7 @@ PENNY_API int penny_moe_gemm_prefill_fp8(const void* X, int ldx, const int* rows
   const dim3 grid((unsigned)(((P + TM - 1) / TM + E) * (N / TN)));
 #define MOE_TILE(EPI_, BAL_)                                                                                    \
   hipLaunchKernelGGL((gemm_prefill_kernel<EPI_, 0, BAL_, true>), grid, dim3(512), 0, stream, X, ldx, W, K, Y, ldy, \
-                     (const bf16*)nullptr, 0, P, N, 1, RopeArgs{}, ma, SampleArgs{}, TailArgs{})
+                     (const bf16*)nullptr, 0, P, N, 1, RopeArgs{}, ma, SampleArgs{}, TailArgs{}, LogprobArgs{})
   if (plain) {
     if (epi == EPI_MOE_SILU) MOE_TILE(EPI_MOE_SILU, 0);
     else MOE_TILE(EPI_MOE_ROUTE, 0);
@@ -1013,10 +1068,12 @@ PENNY_API int penny_moe_gemm_prefill_fp8_mx(const void* X, int ldx, const int* r
   const dim3 grid((unsigned)(((P + TM - 1) / TM + E) * (N / TN)));
   if (epi == EPI_MOE_SILU_MX)
     hipLaunchKernelGGL((gemm_prefill_kernel<EPI_MOE_SILU_MX, 0, 1, true>), grid, dim3(512), 0, stream, X, ldx, W, K,
-                       Y, ldy, (const bf16*)nullptr, 0, P, N, 1, RopeArgs{}, ma, SampleArgs{}, TailArgs{});
+                       Y, ldy, (const bf16*)nullptr, 0, P, N, 1, RopeArgs{}, ma, SampleArgs{}, TailArgs{},
+                       LogprobArgs{});
   else
     hipLaunchKernelGGL((gemm_prefill_kernel<EPI_MOE_ROUTE_MX, 0, 1, true>), grid, dim3(512), 0, stream, X, ldx, W, K,
-                       Y, ldy, (const bf16*)nullptr, 0, P, N, 1, RopeArgs{}, ma, SampleArgs{}, TailArgs{});
+                       Y, ldy, (const bf16*)nullptr, 0, P, N, 1, RopeArgs{}, ma, SampleArgs{}, TailArgs{},
+                       LogprobArgs{});
   return (int)hipGetLastError();
 }
 
@@ -1102,7 +1159,8 @@ PENNY_API int penny_lm_head_sample(const void* X, int ldx, const void* W, int K,
   int* pi = reinterpret_cast<int*>(pv + (long)M * P);
   const SampleArgs sa{temps, seeds, pv, pi, 0, V};
   hipLaunchKernelGGL((gemm_prefill_kernel<EPI_SAMPLE>), grid_for(M, V, 1), dim3(512), 0, stream, X, ldx, W, K,
-                     nullptr, 0, (const bf16*)nullptr, 0, M, V, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{});
+                     nullptr, 0, (const bf16*)nullptr, 0, M, V, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{},
+                     LogprobArgs{});
   hipLaunchKernelGGL(lm_sample_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, P, out, (int*)nullptr);
   return (int)hipGetLastError();
 }
@@ -1124,7 +1182,91 @@ PENNY_API int penny_lm_head_sample_shard(const void* X, int ldx, const void* W, 
   int* pi = reinterpret_cast<int*>(pv + (long)M * P);
   const SampleArgs sa{temps, seeds, pv, pi, voff, vvalid};
   hipLaunchKernelGGL((gemm_prefill_kernel<EPI_SAMPLE>), grid_for(M, Vpad, 1), dim3(512), 0, stream, X, ldx, W, K,
-                     nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{});
+                     nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{},
+                     LogprobArgs{});
   hipLaunchKernelGGL(lm_sample_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, P, (int*)nullptr, pairs);
+  return (int)hipGetLastError();
+}
+
+// Reduce a row's partials of the fused LM-head log-likelihood (EPI_LOGPROB) to stats[row] =
+// {Mx, S, tl, top1 bits}: Mx the row's max logit, S = sum exp(l - Mx), tl the target's logit
+// (-inf: no target / not in this shard), top1 the argmax id (ties to the smallest id); logprob[row]
+// = tl - Mx - log S when asked for.  One 256-thread workgroup per row, as lm_sample_final_kernel.
+__global__ void __launch_bounds__(256) lm_logprob_final_kernel(const float* __restrict__ pm,
+                                                               const float* __restrict__ ps,
+                                                               const float* __restrict__ pt,
+                                                               const int* __restrict__ pa, int P,
+                                                               float* __restrict__ stats, float* __restrict__ logprob) {
+  __shared__ float sv[4], st[4], ss[4];
+  __shared__ int si[4];
+  const long row = blockIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float bv = -INFINITY, tl = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int j = threadIdx.x; j < P; j += 256) {
+    better(bv, bi, pm[row * P + j], pa[row * P + j]);
+    tl = fmaxf(tl, pt[row * P + j]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    better(bv, bi, ov, oi);
+    tl = fmaxf(tl, __shfl_xor(tl, o, 64));
+  }
+  if (lane == 0) {
+    sv[w] = bv;
+    si[w] = bi;
+    st[w] = tl;
+  }
+  __syncthreads();
+  bv = sv[0], bi = si[0], tl = st[0];
+  for (int k = 1; k < 4; ++k) {
+    better(bv, bi, sv[k], si[k]);
+    tl = fmaxf(tl, st[k]);
+  }
+  // bv = Mx in every thread; partials without a valid column (ps == 0, pm == -inf) are skipped
+  float s = 0.f;
+  for (int j = threadIdx.x; j < P; j += 256) {
+    const float p = ps[row * P + j];
+    if (p != 0.f) s += p * __expf(pm[row * P + j] - bv);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) ss[w] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+    stats[4 * row] = bv;
+    stats[4 * row + 1] = s;
+    stats[4 * row + 2] = tl;
+    stats[4 * row + 3] = __int_as_float(bi);
+    if (logprob) logprob[row] = tl - bv - logf(s);
+  }
+}
+
+// LM head + log-likelihood fused: for row m of X [M, K] bf16 x W [Vpad, K]^T (global vocabulary rows
+// voff .. voff + vvalid - 1, then padding), stats [M, 4] = {max logit, sum exp(l - max), logit of
+// targets[m] (-inf when < 0 or outside the shard), argmax id as int bits} over the bf16-rounded
+// logits, and logprob [M] = log softmax at the target (nullable; meaningful for a whole vocabulary,
+// shards are merged from their stats) -- the [M, Vpad] logits are never written.
+// workspace: 4 * M * 2 * (Vpad / 256) floats.
+// Contract (checked): Vpad % 256 == 0, 0 < vvalid <= Vpad, voff >= 0, K % 64 == 0, ldx % 8 == 0.
+PENNY_API int penny_lm_head_logprob(const void* X, int ldx, const void* W, int K, int M, int Vpad, int vvalid,
+                                    int voff, const int* targets, void* workspace, float* stats, float* logprob,
+                                    hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (Vpad % TN || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % BK || ldx % 8 || !targets || !workspace || !stats)
+    return (int)hipErrorInvalidValue;
+  const int P = 2 * (Vpad / TN);
+  float* pm = static_cast<float*>(workspace);
+  float* ps = pm + (long)M * P;
+  float* pt = ps + (long)M * P;
+  int* pa = reinterpret_cast<int*>(pt + (long)M * P);
+  const LogprobArgs la{targets, pm, ps, pt, pa, voff, vvalid};
+  hipLaunchKernelGGL((gemm_prefill_kernel<EPI_LOGPROB>), grid_for(M, Vpad, 1), dim3(512), 0, stream, X, ldx, W, K,
+                     nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, SampleArgs{}, TailArgs{},
+                     la);
+  hipLaunchKernelGGL(lm_logprob_final_kernel, dim3(M), dim3(256), 0, stream, pm, ps, pt, pa, P, stats, logprob);
   return (int)hipGetLastError();
 }

@@ -19,7 +19,7 @@ from typing import AsyncIterator, Dict, List, Optional, Sequence as Seq, Tuple
 from ..config import EngineConfig
 from ..utils.logging import get_logger
 from ..utils.metrics import METRICS
-from .llm_engine import LLMEngine, StepOutput
+from .llm_engine import LLMEngine, ScoreResult, StepOutput
 from .sequence import SamplingParams
 
 logger = get_logger(__name__)
@@ -29,6 +29,15 @@ _rid = itertools.count()
 def _deliver(items) -> None:
     for q, o in items:
         q.put_nowait(o)
+
+
+def _resolve(fut: asyncio.Future, res) -> None:
+    if fut.done():          # the awaiting task was cancelled
+        return
+    if isinstance(res, BaseException):
+        fut.set_exception(res)
+    else:
+        fut.set_result(res)
 
 
 class AsyncEngine:
@@ -42,6 +51,8 @@ class AsyncEngine:
         self._wake = threading.Event()
         self._pending: List[Tuple[str, Seq[int], SamplingParams]] = []
         self._aborts: List[str] = []
+        # score() calls: (token ids, caller's loop, its future), run by the engine thread between steps
+        self._scores: List[Tuple[List[int], asyncio.AbstractEventLoop, asyncio.Future]] = []
         self._sinks: Dict[str, Tuple[asyncio.AbstractEventLoop, asyncio.Queue]] = {}
         self._stop = False
         self.error: Optional[BaseException] = None
@@ -89,8 +100,18 @@ class AsyncEngine:
             with self._lock:
                 pending, self._pending = self._pending, []
                 aborts, self._aborts = self._aborts, []
+                scores, self._scores = self._scores, []
             for rid in aborts:
                 eng.abort(rid)
+            for ids, loop, fut in scores:
+                try:
+                    res = eng.score(ids)
+                except Exception as e:  # noqa: BLE001 - the caller's await raises it
+                    res = e
+                try:
+                    loop.call_soon_threadsafe(_resolve, fut, res)
+                except RuntimeError:  # loop closed
+                    pass
             for rid, ids, params in pending:
                 try:
                     eng.add_request(rid, ids, params)
@@ -196,6 +217,16 @@ class AsyncEngine:
         async for o in self.generate(prompt_ids, params):
             last = o
         return last
+
+    async def score(self, prompt_ids: Seq[int]) -> ScoreResult:
+        """``LLMEngine.score`` from the event loop: queued like a submission and run by the engine
+        thread between two steps, so it never races a step for the engine's state."""
+        loop = asyncio.get_running_loop()
+        fut: asyncio.Future = loop.create_future()
+        with self._lock:
+            self._scores.append((list(prompt_ids), loop, fut))
+        self._wake.set()
+        return await fut
 
     def stats(self) -> Dict[str, float]:
         s = self.engine.stats()

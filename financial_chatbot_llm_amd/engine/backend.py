@@ -90,6 +90,18 @@ class EngineLLM(LLMBackend):
         self.last_prompt_tokens = len(ids)
         return ids
 
+    async def score(self, text: str) -> dict:
+        """Log-likelihood of ``text`` under the served model (``LLMEngine.score``): the plain
+        tokenisation, no chat template.  Natural-log units; perplexity = exp(nll_mean)."""
+        import math
+        ids = self.tok.encode(text, allow_special=False)
+        res = await self.engine.score(ids)
+        n = len(res.logprobs)
+        nll = -sum(res.logprobs) / n
+        return {"tokens": len(ids), "logprobs": list(res.logprobs), "nll_mean": nll,
+                "perplexity": math.exp(nll) if nll < 700 else float("inf"),
+                "top1_accuracy": sum(res.top1_match) / n}
+
     async def agenerate(self, messages, tools=None, temperature=0.5, max_tokens=256, **kw) -> LLMResult:
         tools = list(tools or [])
         ids = self._encode(messages, tools, max_tokens)

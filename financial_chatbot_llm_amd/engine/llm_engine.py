@@ -12,6 +12,7 @@ import time
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence as Seq, Tuple
 
+import numpy as np
 import torch
 
 from ..config import EngineConfig
@@ -24,7 +25,8 @@ from ..utils.logging import get_logger
 from ..utils.metrics import METRICS
 from ..utils.profiling import StepProfiler, marker
 from .block_manager import make_block_manager
-from .model_runner import CollectiveTimeout, ModelRunner, StepInputs, build_step_inputs, sample_rows
+from .model_runner import (CollectiveTimeout, ModelRunner, StepInputs, build_step_inputs, prefill_step_inputs,
+                           sample_rows)
 from .scheduler import Scheduler, StepCostModel
 from .sequence import PENDING, SamplingParams, Sequence, SeqStatus
 from .speculative import PromptLookup, accept_draft
@@ -41,6 +43,14 @@ class StepOutput:
     finished: bool
     finish_reason: Optional[str]
     seq: Sequence
+
+
+@dataclass
+class ScoreResult:
+    """``LLMEngine.score``: log p(token i+1 | tokens 0..i) for i = 0..n-2, and whether that token
+    was the model's argmax there."""
+    logprobs: List[float]
+    top1_match: List[bool]
 
 
 def plan_kv_blocks(cfg: EngineConfig, model, device) -> int:
@@ -89,6 +99,7 @@ class LLMEngine:
         self.requests: Dict[str, Sequence] = {}
         self.timing = {"prepare_s": 0.0, "execute_s": 0.0, "post_s": 0.0}   # host-side step anatomy
         self.spec_stats = {"proposed": 0, "accepted": 0}   # prompt-lookup draft tokens
+        self.scored_tokens = 0     # prompt tokens given a log-probability by score()
         self.async_scheduling = bool(getattr(cfg, "async_scheduling", True))
         self._inflight = None      # (batch, samplers, PendingStep) of the step on the GPU
         self.ps = pstate()
@@ -628,8 +639,43 @@ class LLMEngine:
             self.step()
         return [s.output_ids for s in seqs]
 
+    def score(self, prompt_ids: Seq[int]) -> ScoreResult:
+        """Log-likelihood of a token sequence under the model, on the serving kernels: for each of the
+        n - 1 next-token positions, log p(prompt_ids[i + 1] | prompt_ids[:i + 1]) (temperature 1,
+        bf16-rounded logits) and whether that token is the argmax.  Synchronous; call it between
+        ``step()``s on the thread that owns the engine.  The prompt runs as prefill chunks of at most
+        ``max_num_batched_tokens`` rows on KV blocks borrowed for the call: no prefix-cache lookup
+        (every row is computed) and nothing committed to the cache; the blocks go back on return."""
+        ids = list(prompt_ids)
+        if len(ids) < 2:
+            raise ValueError("score() needs at least 2 tokens")
+        if len(ids) > self.cfg.max_model_len:
+            raise ValueError(f"score(): {len(ids)} tokens exceed max_model_len = {self.cfg.max_model_len}")
+        if self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None:
+            raise NotImplementedError("score(): TP / CP engines do not broadcast scoring steps yet")
+        rows = len(ids) - 1                 # the last token is only ever a target
+        seq = Sequence(f"score-{id(ids)}", ids[:rows], SamplingParams(temperature=0.0, max_tokens=1))
+        if not self.bm.grow(seq, rows):
+            raise RuntimeError(f"score(): {self.bm.blocks_needed(seq, rows)} KV blocks needed, "
+                               f"{self.bm.num_free()} free")
+        logprobs: List[float] = []
+        match: List[bool] = []
+        try:
+            chunk = max(1, int(self.cfg.max_num_batched_tokens))
+            for start in range(0, rows, chunk):
+                n = min(chunk, rows - start)
+                tg = np.asarray(ids[start + 1:start + n + 1], np.int32)
+                lp, top1 = self.runner.score_chunk(prefill_step_inputs(seq, start, n), tg)
+                logprobs += lp
+                match += [int(a) == int(b) for a, b in zip(top1, tg)]
+        finally:
+            self.bm.free(seq)
+        self.scored_tokens += rows
+        return ScoreResult(logprobs, match)
+
     def stats(self) -> Dict[str, float]:
         return {"running": len(self.scheduler.running), "waiting": len(self.scheduler.waiting),
+                "scored_tokens": self.scored_tokens,
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),
                 "preemptions": self.scheduler.num_preemptions,

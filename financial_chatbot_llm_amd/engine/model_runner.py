@@ -212,6 +212,19 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
                       src_a)
 
 
+def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
+    """A prefill-only step of prompt tokens [start, start + n) of one sequence that samples nothing
+    (prompt scoring): its rows attend to the sequence's first start + n tokens through its block
+    table, like a scheduled prefill chunk."""
+    p = np.arange(start, start + n, dtype=np.int32)
+    bt = np.asarray(seq.block_table, np.int32)
+    e = np.zeros(0, np.int32)
+    return StepInputs(np.asarray(seq.prompt_ids[start:start + n], np.int32), p, bt[p // KV_BS] * KV_BS + p % KV_BS,
+                      np.asarray([0, n], np.int32), np.asarray([start + n], np.int32), _table([seq.block_table]), n,
+                      e, _table([]), np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros(0, np.int64), e,
+                      np.zeros(0, np.float32), None)
+
+
 class CollectiveTimeout(RuntimeError):
     """A device-side collective (custom xGMI all-reduce) reported a missing peer."""
 
@@ -558,6 +571,30 @@ class ModelRunner:
 
     def _forward_only(self, si: StepInputs) -> None:
         self._hidden(si)
+
+    def score_chunk(self, si: StepInputs, targets: np.ndarray) -> Tuple[List[float], List[int]]:
+        """Prompt scoring: forward a prefill-only step and return, for every row whose ``targets``
+        entry ([T] int32, < 0: none) names the token that follows it, log p(target | row) and the
+        row's argmax token (``model.token_logprobs``: no [T, V] logits).  Synchronous, on the current
+        stream after whatever step is in flight; apart from the KV slots the step names it touches
+        no runner state (no ``launch()``, output ring, ``last_sampled`` or decode graph)."""
+        if si.num_decode or si.src is not None or len(si.logits_idx):
+            raise ValueError("score_chunk takes a prefill-only step without sampled rows")
+        rows = np.flatnonzero(np.asarray(targets) >= 0)
+        if si.pwork is None and self.on_gpu:
+            si.pwork = prefill_plan(si.cu_q, si.ctx_p, self.G, self.model.hkv)
+        self._stage_inputs(si)
+        try:
+            h = self._hidden(si)
+        finally:
+            self._staged = None
+        if len(rows) == 0:
+            return [], []
+        tg = torch.from_numpy(np.ascontiguousarray(np.asarray(targets, np.int32)[rows])).to(self.device)
+        if len(rows) < len(si.ids):
+            h = h.index_select(0, torch.from_numpy(rows).to(self.device))
+        lp, top1 = self.model.token_logprobs(h, tg)
+        return lp.float().cpu().tolist(), top1.cpu().tolist()
 
     def drop_graphs(self) -> None:
         """Forget every captured decode graph (they bake in the custom all-reduce kernels and its

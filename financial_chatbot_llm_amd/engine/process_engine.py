@@ -34,11 +34,13 @@ from typing import AsyncIterator, Dict, List, Optional, Sequence as Seq, Tuple
 
 from ..config import EngineConfig
 from ..utils.logging import get_logger
-from .llm_engine import StepOutput
+from .async_engine import _resolve
+from .llm_engine import ScoreResult, StepOutput
 from .sequence import SamplingParams
 
 logger = get_logger(__name__)
 _rid = itertools.count()
+_SCORE_ERRORS = {"ValueError": ValueError, "NotImplementedError": NotImplementedError, "RuntimeError": RuntimeError}
 
 
 @dataclass
@@ -87,6 +89,12 @@ def _engine_main(cfg: EngineConfig, device_index: Optional[int], req_conn, out_c
                         out_conn.send(("error", rid, f"{type(e).__name__}: {e}"))
                 elif kind == "abort":
                     eng.abort(msg[1])
+                elif kind == "score":     # between two steps, like every control message
+                    try:
+                        res = eng.score(msg[2])
+                        out_conn.send(("score", msg[1], (res.logprobs, res.top1_match), None))
+                    except Exception as e:  # noqa: BLE001 - raised again in the caller
+                        out_conn.send(("score", msg[1], None, (type(e).__name__, str(e))))
                 elif kind == "stats":
                     s = eng.stats()
                     if step_times:
@@ -150,6 +158,7 @@ class ProcessAsyncEngine:
         self._send_lock = threading.Lock()
         self._sinks: Dict[str, Tuple[asyncio.AbstractEventLoop, asyncio.Queue]] = {}
         self._seqs: Dict[str, RemoteSeq] = {}
+        self._score_waiters: Dict[int, Tuple[asyncio.AbstractEventLoop, asyncio.Future]] = {}
         self._stats_evt = threading.Event()
         self._stats: Dict[str, float] = {}
         self.error: Optional[BaseException] = None
@@ -202,6 +211,17 @@ class ProcessAsyncEngine:
                         loop.call_soon_threadsafe(_deliver, items)
                     except RuntimeError:
                         pass
+            elif kind == "score":
+                waiter = self._score_waiters.pop(msg[1], None)
+                if waiter is not None:
+                    if msg[3] is None:
+                        res = ScoreResult(*msg[2])
+                    else:
+                        res = _SCORE_ERRORS.get(msg[3][0], RuntimeError)(msg[3][1])
+                    try:
+                        waiter[0].call_soon_threadsafe(_resolve, waiter[1], res)
+                    except RuntimeError:
+                        pass
             elif kind == "stats":
                 self._stats = msg[1]
                 self._stats_evt.set()
@@ -227,6 +247,12 @@ class ProcessAsyncEngine:
     def _fail_all(self, err: BaseException) -> None:
         for rid in list(self._sinks):
             self._emit(rid, err)
+        for sid in list(self._score_waiters):
+            loop, fut = self._score_waiters.pop(sid)
+            try:
+                loop.call_soon_threadsafe(_resolve, fut, err)
+            except RuntimeError:
+                pass
 
     def _send(self, msg) -> None:
         with self._send_lock:
@@ -262,6 +288,18 @@ class ProcessAsyncEngine:
         async for o in self.generate(prompt_ids, params):
             last = o
         return last
+
+    async def score(self, prompt_ids: Seq[int]) -> ScoreResult:
+        """``LLMEngine.score`` in the child, between two of its steps."""
+        loop = asyncio.get_running_loop()
+        fut: asyncio.Future = loop.create_future()
+        sid = next(_rid)
+        self._score_waiters[sid] = (loop, fut)
+        try:
+            self._send(("score", sid, list(prompt_ids)))
+            return await fut
+        finally:
+            self._score_waiters.pop(sid, None)
 
     def stats(self, timeout_s: float = 30.0) -> Dict[str, float]:
         self._stats_evt.clear()

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -498,6 +498,20 @@ class DecoderModel:
         else:
             pairs = ops.sample_shard(linear(h, w), temps, seeds, self.vocab_start, self.cfg.vocab_size)
         return ops.pick_pairs(comm.tp_all_gather_pairs(pairs))
+
+    def token_logprobs(self, h: torch.Tensor, targets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Prompt scoring: (log p(targets[m] | row m) [M] f32, argmax token [M] int32) from the final
+        hidden states ``h`` [M, H], at temperature 1 on the bf16-rounded logits and without the
+        [M, V] logits (``ops.lm_head_logprobs``).  Under TP each rank reduces its own (padded) vocab
+        shard to [M, 4] stats, which are all-gathered and merged: no logits all-gather either."""
+        w = self.lm_weight()
+        if self.tp_size == 1:
+            stats = ops.lm_head_logprobs(h, w, targets, return_stats=True)
+            return ops.merge_logprob_stats(stats[None])
+        pad = getattr(self, "_lm_pad", None)
+        stats = ops.lm_head_logprobs(h, w if pad is None else pad, targets, vvalid=w.shape[0], voff=self.vocab_start,
+                                     return_stats=True)
+        return ops.merge_logprob_stats(comm.tp_all_gather_pairs(stats))
 
 
 class LlamaModel(DecoderModel):

@@ -68,6 +68,7 @@ _SIGS = {
     "penny_sample": [P, c_int, c_long, P, P, P, P, P, P, c_int, c_int, P],
     "penny_lm_head_sample": [P, c_int, P, c_int, c_int, c_int, P, P, P, P, P],
     "penny_lm_head_sample_shard": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],
+    "penny_lm_head_logprob": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],
     "penny_sample_shard": [P, c_int, c_long, P, P, P, P, c_int, c_int, c_int, P],
     "penny_topk_topp_threshold": [P, c_int, c_long, P, P, P, P, c_int, c_int, P],
     "penny_moe_route": [P, c_int, c_int, c_int, P, P, P, P, P],

@@ -231,6 +231,83 @@ def pick_pairs(allp: torch.Tensor) -> torch.Tensor:
     return cand.min(0).values.to(torch.int32)
 
 
+# ----------------------------------------------------------------------------------------------
+# Prompt scoring: the log-likelihood sibling of the fused LM head + sampler.  The tile kernel's
+# EPI_LOGPROB epilogue reduces every (row, 128-column wave half) of the bf16-rounded logits to its
+# (max, sum of exp(l - max), target logit, argmax id); a merge kernel reduces a row's partials to
+# stats [M, 4] = {Mx, S, tl, top1 bits} -- no [M, V] logits and no f32 softmax copy in HBM.
+# log p(target) = tl - Mx - log S, at temperature 1.  Vocabulary shards (TP) merge their stats
+# with ``merge_logprob_stats``.  ``PENNY_FUSED_LOGPROB=0`` forces the reference path (logits ->
+# f32 log-softmax -> gather), which is also what CPU tensors run.
+# ----------------------------------------------------------------------------------------------
+def fused_logprob_ok(h: torch.Tensor, w: torch.Tensor) -> bool:
+    """True when :func:`lm_head_logprobs` takes the tile kernel (at every M, down to one row)."""
+    import os
+    if os.environ.get("PENNY_FUSED_LOGPROB", "1") == "0" or not N.use_native(h):
+        return False
+    K = h.shape[1]
+    return not (w.shape[0] % 256 or K % 64 or h.stride(1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16
+                or not w.is_contiguous() or h.dtype != torch.bfloat16 or w.dtype != torch.bfloat16)
+
+
+def _pack_stats(mx: torch.Tensor, s: torch.Tensor, tl: torch.Tensor, top1: torch.Tensor) -> torch.Tensor:
+    """{Mx, S, tl, top1 bits} rows as one f32 [M, 4] tensor (moved as integers: the id's bit pattern
+    is no float to compute with)."""
+    st = torch.stack([mx.float().view(torch.int32), s.float().view(torch.int32), tl.float().view(torch.int32),
+                      top1.to(torch.int32)], -1)
+    return st.view(torch.float32)
+
+
+def lm_head_logprobs(h: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, vvalid: Optional[int] = None,
+                     voff: int = 0, return_stats: bool = False) -> torch.Tensor:
+    """log softmax(h @ w.T)[targets] per row of ``h`` [M, K], over the bf16-rounded logits at
+    temperature 1, without materialising them.  ``w`` [Vpad, K] holds global vocabulary rows
+    voff .. voff+vvalid-1, then padding; ``targets`` [M] are global token ids (< 0: no target,
+    logprob -inf).  Returns logprob [M] f32, or (``return_stats``) stats [M, 4] f32 = {max logit,
+    sum exp(l - max), target logit (-inf when absent from this shard), argmax id as int32 bits,
+    ties to the smallest id} -- what :func:`merge_logprob_stats` combines across shards."""
+    M, K = h.shape
+    Vpad = w.shape[0]
+    vvalid = Vpad if vvalid is None else int(vvalid)
+    if not 0 < vvalid <= Vpad or voff < 0:
+        raise ValueError(f"vocab shard [{voff}, {voff}+{vvalid}) does not fit {Vpad} weight rows")
+    tg = targets.to(device=h.device, dtype=torch.int32).contiguous()
+    if fused_logprob_ok(h, w):
+        stats = torch.empty((M, 4), dtype=torch.float32, device=h.device)
+        lp = None if return_stats else torch.empty((M,), dtype=torch.float32, device=h.device)
+        ws = torch.empty((4 * M * 2 * (Vpad // 256),), dtype=torch.float32, device=h.device)
+        N.call("penny_lm_head_logprob", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, vvalid, int(voff), N.ptr(tg),
+               N.ptr(ws), N.ptr(stats), N.ptr(lp), N.stream())
+        return stats if return_stats else lp
+    from .gemm import linear
+    lf = linear(h, w[:vvalid]).float()          # logits in the activation dtype (bf16 on the device)
+    mx = lf.max(-1).values
+    s = torch.exp(lf - mx[:, None]).sum(-1)
+    ids = torch.arange(vvalid, device=h.device, dtype=torch.int32)[None, :]
+    top1 = torch.where(lf == mx[:, None], ids, torch.full_like(ids, 0x7FFFFFFF)).min(-1).values + int(voff)
+    loc = tg.long() - int(voff)
+    inside = (tg >= 0) & (loc >= 0) & (loc < vvalid)
+    tl = lf.gather(1, loc.clamp(0, vvalid - 1)[:, None])[:, 0]
+    tl = torch.where(inside, tl, torch.full_like(tl, float("-inf")))
+    if return_stats:
+        return _pack_stats(mx, s, tl, top1)
+    return tl - mx - torch.log(s)
+
+
+def merge_logprob_stats(all_stats: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[R, M, 4] stats of R vocabulary shards -> (logprob [M] f32, top1 [M] int32), by the merge
+    kernel's formulas: Mx = max Mx_r, S = sum S_r exp(Mx_r - Mx) (a shard with S_r == 0 holds no
+    column and contributes nothing), tl = max tl_r, top1 from (Mx_r, id_r) with ties to the smallest
+    id.  Device ops only (graph-capturable)."""
+    st = all_stats.contiguous()
+    mx, s, tl = st[..., 0], st[..., 1], st[..., 2]
+    ids = st.view(torch.int32)[..., 3]
+    g = mx.max(0, keepdim=True).values
+    part = torch.where(s > 0, s * torch.exp(mx - g), torch.zeros_like(s))
+    top1 = torch.where((mx == g) & (s > 0), ids, torch.full_like(ids, 0x7FFFFFFF)).min(0).values
+    return tl.max(0).values - g[0] - torch.log(part.sum(0)), top1.to(torch.int32)
+
+
 def topk_topp_threshold(logits: torch.Tensor, temperatures: torch.Tensor, top_k: torch.Tensor,
                         top_p: torch.Tensor) -> torch.Tensor:
     """The HIP filter's per-row logit threshold (-inf: keep all) -- diagnostics/tests."""

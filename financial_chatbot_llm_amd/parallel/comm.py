@@ -225,25 +225,26 @@ def tp_all_gather_last(x: torch.Tensor) -> torch.Tensor:
 def tp_all_gather_pairs(pairs: torch.Tensor) -> torch.Tensor:
     """Vocab-parallel sampling candidates: every rank's [B, 2] int32 (score bits, token id) ->
     [tp, B, 2] in rank order.  The custom xGMI gather moves the bytes as bf16 (graph-capturable);
-    RCCL / gloo otherwise."""
+    RCCL / gloo otherwise.  Any [B, C] of a 4-byte dtype with C even travels the same way (the
+    [B, 4] f32 log-likelihood stats of ``token_logprobs``) -> [tp, B, C]."""
     s = state()
     if s.tp_size == 1:
         return pairs[None]
-    B = pairs.shape[0]
+    B, C = pairs.shape
     x = pairs.contiguous()
-    if B % 2:                                    # the bf16 view must be a multiple of 8 elements
+    if (B * C) % 4:                              # the bf16 view must be a multiple of 8 elements
         x = torch.cat([x, x[:1]], 0)
     xb = x.view(torch.bfloat16)
     if _CUSTOM_AR is not None and _CUSTOM_AR.gather_eligible(xb):
-        g = _CUSTOM_AR.all_gather(xb)            # [tp, B', 4] bf16
-        return g.view(torch.int32).view(s.tp_size, -1, 2)[:, :B]
+        g = _CUSTOM_AR.all_gather(xb)            # [tp, B', 2C] bf16
+        return g.view(x.dtype).view(s.tp_size, -1, C)[:, :B]
     if _is_gloo(s.tp_group):
         parts = [torch.empty_like(x) for _ in range(s.tp_size)]
         dist.all_gather(parts, x, group=s.tp_group)
         return torch.stack(parts, 0)[:, :B]
-    out = torch.empty((s.tp_size * x.shape[0], 2), dtype=x.dtype, device=x.device)
+    out = torch.empty((s.tp_size * x.shape[0], C), dtype=x.dtype, device=x.device)
     dist.all_gather_into_tensor(out, x, group=s.tp_group)
-    return out.view(s.tp_size, -1, 2)[:, :B]
+    return out.view(s.tp_size, -1, C)[:, :B]
 
 
 def _is_gloo(group) -> bool:
