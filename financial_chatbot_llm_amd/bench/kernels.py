@@ -611,6 +611,58 @@ def bench_lm_head_logprob(dev, Ms=(256, 2048, 8192)) -> List[Dict]:
     return out
 
 
+def bench_constrained_sample(dev, Ms=(16, 64, 128, 256), V: int = 128256, K: int = 4096) -> List[Dict]:
+    """Constrained tool-call decoding (ops.sample_constrained, vocab 128256, K 4096), variants timed in
+    interleaved rounds: (a) penny_sample_fsm (half the rows constrained, in string / key / number
+    states of the two-tool automaton) against penny_sample on the same logits; (b) the per-step
+    price of one constrained row -- the fused LM head + sampler against logits (the model's LM-head
+    GEMM) + sample_constrained; (c) the mask build for the real two-tool automaton."""
+    from ..agent.automaton import compile_tool_automaton
+    from ..engine.tokenizer import SyntheticLlamaTokenizer
+    from ..ops import gemm
+    from ..tools import make_plot_tool, make_retrieval_tool
+    gemm.load_gemm_tuning("llama3-8b")
+    a = compile_tool_automaton([make_retrieval_tool(None), make_plot_tool()], SyntheticLlamaTokenizer(V))
+    t = ops.FsmTables(4096, V, a.tok_off, a.tok_bytes, a.eot_id, dev)
+    off = t.add(a.byte_next, a.accept, a.done)
+    out = []
+    build = timeit(lambda: ops.build_masks(t, off, a.num_states), iters=3, rounds=5)
+    out.append({"op": "fsm_build_masks", "states": a.num_states, "V": V, "mask_MiB": round(a.num_states * t.W * 4 / 2 ** 20, 1),
+                "build_us": round(build, 1), "walks_per_us": round(a.num_states * V / build, 1)})
+    head = '{"name": "retrieve_transactions", "parameters": {'
+    spots = [a.start, a.walk(a.start, (head + '"search_query": "gro').encode()), a.walk(a.start, (head + '"').encode()),
+             a.walk(a.start, (head + '"num_transactions": 2').encode())]
+    w = torch.randn((V, K), device=dev).to(torch.bfloat16) * 0.02
+    for M in Ms:
+        x = torch.randn((M, K), device=dev).to(torch.bfloat16)
+        temps = torch.full((M,), 0.7, device=dev)
+        sd = torch.arange(M, dtype=torch.int64, device=dev) * 977
+        logits = gemm.linear(x, w)
+        half = torch.tensor([off + spots[(r // 2) % 4] if r % 2 == 0 else -1 for r in range(M)], dtype=torch.int32,
+                            device=dev)
+        one = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        one[0] = off + spots[1]
+        free = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        r = interleaved({
+            "sample": lambda: ops.sample(logits, temps, sd),
+            "sample_fsm_half": lambda: ops.sample_constrained(logits, temps, sd, half, t),
+            "sample_fsm_none": lambda: ops.sample_constrained(logits, temps, sd, free, t),
+            "fused_lm_head": lambda: ops.lm_head_sample(x, w, temps, sd),
+            "logits_plus_fsm": lambda: ops.sample_constrained(gemm.linear(x, w), temps, sd, one, t),
+            "logits_only": lambda: gemm.linear(x, w),
+        }, rounds=9, iters=50)
+        same = bool(torch.equal(ops.sample_constrained(logits, temps, sd, free, t)[0], ops.sample(logits, temps, sd)))
+        out.append({"op": "constrained_sample", "M": M, "V": V, "K": K,
+                    "sample_us": round(r["sample"], 1), "sample_fsm_half_rows_us": round(r["sample_fsm_half"], 1),
+                    "sample_fsm_no_rows_us": round(r["sample_fsm_none"], 1),
+                    "fused_lm_head_us": round(r["fused_lm_head"], 1), "logits_us": round(r["logits_only"], 1),
+                    "logits_plus_sample_fsm_us": round(r["logits_plus_fsm"], 1),
+                    "step_price_us": round(r["logits_plus_fsm"] - r["fused_lm_head"], 1),
+                    "unconstrained_rows_equal_sample": same})
+        print(json.dumps(out[-1]), flush=True)
+    return out
+
+
 def bench_bge_query(dev) -> List[Dict]:
     """bge-base encoder latency on retrieval-size query batches (the per-turn critical path): the
     four projections on hipBLASLt (+ the GELU pass) vs the tile kernel with the bias / bias+GELU
@@ -1653,6 +1705,7 @@ def main(argv=None) -> int:
                                                         Ms=(96, 112, 128, 144, 160, 192, 256)), "chunked_prefill": bench_chunked_prefill,
                 "shard_shapes_tp8": lambda d: bench_shard_shapes(d, [n for n in SHARD_SHAPES if "tp8" in n]),
                 "shard_shapes_tp1": lambda d: bench_shard_shapes(d, [n for n in SHARD_SHAPES if "tp1" in n]),
+                "constrained_sample": bench_constrained_sample,
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),
                 "lm_head_stream_shard": lambda d: bench_lm_head_stream(d, V=16128, Ms=(1, 8, 32, 64, 127))}[name](dev)
     for r in res:

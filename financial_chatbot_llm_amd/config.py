@@ -162,6 +162,9 @@ class EngineConfig:
     seed: int = 0
     device: str = "cuda"
     step_timeout_s: float = 60.0            # GPU-step watchdog
+    # constrained tool-call decoding (agent.automaton): capacity of the device automaton tables
+    # (allocated at the first constrained request; ~64 MiB of token masks at V = 128256)
+    fsm_max_states: int = 4096
 
     @classmethod
     def from_env(cls, **overrides) -> "EngineConfig":
@@ -197,6 +200,7 @@ class EngineConfig:
             tp_dual_decode=_env_bool("PENNY_TP_DUAL_DECODE", False),
             use_cuda_graph=_env_bool("PENNY_HIPGRAPH", True),
             device=_env("PENNY_DEVICE", cls.device),
+            fsm_max_states=_env_int("PENNY_FSM_MAX_STATES", cls.fsm_max_states),
         )
         return dataclasses.replace(c, **overrides)
 
@@ -244,6 +248,8 @@ class ServingConfig:
     # POST /v1/transactions is only served when an operator token is configured, and every call
     # must present it (Authorization: Bearer <token>); unset = the write path does not exist
     ingest_token: Optional[str] = None
+    # decide calls sample under the tool-call token automaton (schema-valid output); off by default
+    constrain_toolcalls: bool = False
 
     @classmethod
     def from_env(cls, **overrides) -> "ServingConfig":
@@ -256,6 +262,7 @@ class ServingConfig:
             backend=_env("PENNY_BACKEND", cls.backend),
             tools=_env_bool("PENNY_TOOLS", True),
             ingest_token=_env("PENNY_INGEST_TOKEN", "") or None,
+            constrain_toolcalls=_env_bool("PENNY_CONSTRAIN_TOOLCALLS", False),
         )
         return dataclasses.replace(c, **overrides)
 

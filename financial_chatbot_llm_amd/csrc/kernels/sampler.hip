@@ -71,13 +71,32 @@ __device__ __forceinline__ void find_from_top(const float* bins, float target, i
   above = a;
 }
 
-// One 1024-thread workgroup per row -> thresh[row] (a logit; -inf = keep everything).
-template <typename T>
+// Token-automaton constraint (constrain.hip builds the tables): a row in automaton state st >= 0 may
+// only pick tokens whose bit is set in masks[st, :] (W 32-bit words per state, token i = bit i & 31
+// of word i >> 5); every other token counts as -inf.  st < 0: the row is unconstrained.  A state
+// outside the table admits nothing (the row then emits eot).
+struct FsmMask {
+  const int* state;            // [B]
+  const uint32_t* masks;       // [S, W]
+  int W, S;
+};
+__device__ __forceinline__ const uint32_t* fsm_row(const FsmMask& fm, int row, bool& con, bool& none) {
+  const int st = fm.state[row];
+  con = st >= 0;
+  none = st >= fm.S;
+  PENNY_DASSERT(st < fm.S);
+  return fm.masks + (size_t)(con && !none ? st : 0) * fm.W;
+}
+__device__ __forceinline__ bool fsm_bit(const uint32_t* mrow, int i) { return (mrow[i >> 5] >> (i & 31)) & 1u; }
+
+// One 1024-thread workgroup per row -> thresh[row] (a logit; -inf = keep everything).  MASKED: the
+// constraint applies BEFORE top-k / top-p -- disallowed tokens are neither counted nor weighed.
+template <typename T, bool MASKED>
 __global__ void __launch_bounds__(1024) topk_topp_threshold_kernel(const T* __restrict__ logits, long row_stride,
                                                                    const float* __restrict__ temps,
                                                                    const int* __restrict__ topk,
                                                                    const float* __restrict__ topp,
-                                                                   float* __restrict__ thresh, int V) {
+                                                                   float* __restrict__ thresh, int V, FsmMask fm) {
   // per-wave digit histograms in INTEGERS: counts for top-k, probability mass in 2^-44 fixed point
   // for top-p -- integer adds commute, so the threshold is bitwise independent of the order in
   // which waves and lanes reach the atomics (float atomics made the nucleus edge run-dependent)
@@ -95,6 +114,13 @@ __global__ void __launch_bounds__(1024) topk_topp_threshold_kernel(const T* __re
   }
   const T* lr = logits + row * row_stride;
   const float inv_t = 1.f / temp;
+  bool con = false, none = false;
+  const uint32_t* mrow = nullptr;
+  if (MASKED) mrow = fsm_row(fm, row, con, none);
+  if (MASKED && none) {                // nothing admitted: the sampler emits eot whatever the cut
+    if (tid == 0) thresh[row] = -INFINITY;
+    return;
+  }
   uint32_t prefix = 0, pmask = 0;      // selected high digits so far (keys matching are candidates)
   // ---- top-k: radix select of the k-th largest key ---------------------------------------------
   if (do_k) {
@@ -103,6 +129,7 @@ __global__ void __launch_bounds__(1024) topk_topp_threshold_kernel(const T* __re
       for (int i = tid; i < 16 * 256; i += 1024) (&hist[0][0])[i] = 0ull;
       __syncthreads();
       for (int i = tid; i < V; i += 1024) {
+        if (MASKED && con && !fsm_bit(mrow, i)) continue;
         const uint32_t key = fkey(ld1(lr + i));
         if ((key & pmask) == prefix) atomicAdd(&hist[wid][(key >> shift) & 255], 1ull);
       }
@@ -137,7 +164,10 @@ __global__ void __launch_bounds__(1024) topk_topp_threshold_kernel(const T* __re
   }
   // ---- top-p over the renormalised top-k survivors --------------------------------------------
   float mx = -INFINITY;
-  for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, ld1(lr + i));
+  for (int i = tid; i < V; i += 1024) {
+    if (MASKED && con && !fsm_bit(mrow, i)) continue;
+    mx = fmaxf(mx, ld1(lr + i));
+  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
   if (lane == 0) red[wid] = mx;
@@ -153,6 +183,7 @@ __global__ void __launch_bounds__(1024) topk_topp_threshold_kernel(const T* __re
     for (int i = tid; i < 16 * 256; i += 1024) (&hist[0][0])[i] = 0ull;
     __syncthreads();
     for (int i = tid; i < V; i += 1024) {
+      if (MASKED && con && !fsm_bit(mrow, i)) continue;
       const float l = ld1(lr + i);
       const uint32_t key = fkey(l);
       // exp <= 1 (l <= mx): x 2^44 fits 45 bits, a 128k-entry vocabulary sums below 2^62
@@ -198,13 +229,14 @@ __global__ void __launch_bounds__(1024) topk_topp_threshold_kernel(const T* __re
 // and the per-element noise generation makes this pass VALU-, not bandwidth-, bound).
 #define SAMPLE_SPLITS 16
 
-template <typename T>
+// MASKED: each 8-logit chunk reads one byte of the row's state mask.
+template <typename T, bool MASKED>
 __global__ void __launch_bounds__(256) sample_partial_kernel(const T* __restrict__ logits, long row_stride,
                                                              const float* __restrict__ temps,
                                                              const unsigned long long* __restrict__ seeds,
                                                              const float* __restrict__ thresh,
                                                              float* __restrict__ pv, int* __restrict__ pi, int V,
-                                                             int voff) {
+                                                             int voff, FsmMask fm) {
   __shared__ float sv[4];
   __shared__ int si[4];
   const int row = blockIdx.x, split = blockIdx.y;
@@ -214,18 +246,28 @@ __global__ void __launch_bounds__(256) sample_partial_kernel(const T* __restrict
   const float inv_t = greedy ? 1.f : 1.f / temp;
   const unsigned long long seed = seeds[row];
   const float floor_l = (thresh != nullptr && !greedy) ? thresh[row] : -INFINITY;   // top-k/top-p cut
+  bool con = false, none = false;
+  const uint32_t* mrow = nullptr;
+  if (MASKED) mrow = fsm_row(fm, row, con, none);
+  const uint8_t* mbytes = reinterpret_cast<const uint8_t*>(mrow);
   const int nch = V >> 3;
   const int per = (nch + SAMPLE_SPLITS - 1) / SAMPLE_SPLITS;
   const int c0 = split * per, c1 = min(nch, c0 + per);
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   for (int c = c0 + threadIdx.x; c < c1; c += blockDim.x) {
+    uint32_t mb = 0xffu;
+    if (MASKED && con) {
+      mb = none ? 0u : mbytes[c];
+      if (mb == 0u) continue;
+    }
     float f[8];
     load8<T>(lr + c * 8, f);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int idx = voff + c * 8 + k;     // global token id (vocab shard offset)
       float v = f[k];
+      if (MASKED && !((mb >> k) & 1u)) continue;
       if (v < floor_l) continue;
       if (!greedy) {
         v = v * inv_t + gumbel_noise(seed, idx);
@@ -236,6 +278,7 @@ __global__ void __launch_bounds__(256) sample_partial_kernel(const T* __restrict
   if (split == SAMPLE_SPLITS - 1) {  // tail (V not a multiple of 8)
     for (int loc = (V & ~7) + threadIdx.x; loc < V; loc += blockDim.x) {
       const int idx = voff + loc;
+      if (MASKED && con && (none || !fsm_bit(mrow, loc))) continue;
       float v = (float)lr[loc];
       if (v < floor_l) continue;
       if (!greedy) {
@@ -295,20 +338,20 @@ PENNY_API int penny_sample(const void* logits, int is_fp32, long row_stride, con
   if (top_k != nullptr && top_p != nullptr) {
     th = (float*)(pi + (long)B * SAMPLE_SPLITS);
     if (is_fp32) {
-      hipLaunchKernelGGL(topk_topp_threshold_kernel<float>, dim3(B), dim3(1024), 0, stream, (const float*)logits,
-                         row_stride, temps, top_k, top_p, th, V);
+      hipLaunchKernelGGL((topk_topp_threshold_kernel<float, false>), dim3(B), dim3(1024), 0, stream, (const float*)logits,
+                         row_stride, temps, top_k, top_p, th, V, FsmMask{});
     } else {
-      hipLaunchKernelGGL(topk_topp_threshold_kernel<bf16>, dim3(B), dim3(1024), 0, stream, (const bf16*)logits,
-                         row_stride, temps, top_k, top_p, th, V);
+      hipLaunchKernelGGL((topk_topp_threshold_kernel<bf16, false>), dim3(B), dim3(1024), 0, stream, (const bf16*)logits,
+                         row_stride, temps, top_k, top_p, th, V, FsmMask{});
     }
   }
   dim3 grid(B, SAMPLE_SPLITS);
   if (is_fp32) {
-    hipLaunchKernelGGL(sample_partial_kernel<float>, grid, dim3(256), 0, stream, (const float*)logits, row_stride,
-                       temps, seeds, th, pv, pi, V, 0);
+    hipLaunchKernelGGL((sample_partial_kernel<float, false>), grid, dim3(256), 0, stream, (const float*)logits, row_stride,
+                       temps, seeds, th, pv, pi, V, 0, FsmMask{});
   } else {
-    hipLaunchKernelGGL(sample_partial_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)logits, row_stride,
-                       temps, seeds, th, pv, pi, V, 0);
+    hipLaunchKernelGGL((sample_partial_kernel<bf16, false>), grid, dim3(256), 0, stream, (const bf16*)logits, row_stride,
+                       temps, seeds, th, pv, pi, V, 0, FsmMask{});
   }
   hipLaunchKernelGGL(sample_final_kernel, dim3(B), dim3(64), 0, stream, pv, pi, out, (int*)nullptr);
   PENNY_RETURN_LAUNCH();
@@ -328,13 +371,104 @@ PENNY_API int penny_sample_shard(const void* logits, int is_fp32, long row_strid
   int* pi = (int*)(pv + (long)B * SAMPLE_SPLITS);
   dim3 grid(B, SAMPLE_SPLITS);
   if (is_fp32) {
-    hipLaunchKernelGGL(sample_partial_kernel<float>, grid, dim3(256), 0, stream, (const float*)logits, row_stride,
-                       temps, seeds, (const float*)nullptr, pv, pi, V, voff);
+    hipLaunchKernelGGL((sample_partial_kernel<float, false>), grid, dim3(256), 0, stream, (const float*)logits, row_stride,
+                       temps, seeds, (const float*)nullptr, pv, pi, V, voff, FsmMask{});
   } else {
-    hipLaunchKernelGGL(sample_partial_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)logits, row_stride,
-                       temps, seeds, (const float*)nullptr, pv, pi, V, voff);
+    hipLaunchKernelGGL((sample_partial_kernel<bf16, false>), grid, dim3(256), 0, stream, (const bf16*)logits, row_stride,
+                       temps, seeds, (const float*)nullptr, pv, pi, V, voff, FsmMask{});
   }
   hipLaunchKernelGGL(sample_final_kernel, dim3(B), dim3(64), 0, stream, pv, pi, (int*)nullptr, pairs);
+  PENNY_RETURN_LAUNCH();
+}
+
+// Constrained sampling: the merge of a row's candidates, then one lane advances the row's automaton
+// state over the chosen token's bytes (eot -> the automaton's done state).  A constrained row left
+// without a candidate (its mask admits nothing) emits eot and goes to done; unconstrained rows
+// (state < 0) write state_out = -1.  state_out may alias state.
+struct FsmWalk {
+  const unsigned short* byte_next;   // [S, 256], 0xFFFF = dead
+  const int* tok_off;                // [nt + 1]
+  const unsigned char* tok_bytes;
+  const int* done_of;                // [S] the done state of the automaton each state belongs to
+  int nt, eot;
+};
+
+__global__ void sample_final_fsm_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
+                                        int* __restrict__ out, const int* state, int* state_out, int S,
+                                        FsmWalk fw) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  float bv = lane < SAMPLE_SPLITS ? pv[row * SAMPLE_SPLITS + lane] : -INFINITY;
+  int bi = lane < SAMPLE_SPLITS ? pi[row * SAMPLE_SPLITS + lane] : 0x7fffffff;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    better(bv, bi, ov, oi);
+  }
+  if (lane != 0) return;
+  const int st = state[row];
+  if (st < 0) {
+    out[row] = bi;
+    state_out[row] = -1;
+    return;
+  }
+  if (st >= S) {                      // not a state of the table: nothing admitted, nothing to walk
+    out[row] = fw.eot;
+    state_out[row] = st;
+    return;
+  }
+  int tok = bi, ns = fw.done_of[st];
+  if (bi == 0x7fffffff) tok = fw.eot;
+  if (tok != fw.eot && tok >= 0 && tok < fw.nt) {
+    int cur = st;
+    for (int j = fw.tok_off[tok], e = fw.tok_off[tok + 1]; j < e; ++j) {
+      cur = fw.byte_next[(size_t)cur * 256 + fw.tok_bytes[j]];
+      if (cur >= S) break;            // dead (0xFFFF): an admitted token never dies
+    }
+    PENNY_DASSERT(cur < S);
+    if (cur < S) ns = cur;
+  }
+  out[row] = tok;
+  state_out[row] = ns;
+}
+
+// penny_sample with a token-automaton constraint per row (state[B], < 0: none).  Same noise, tie
+// rule and top-k / top-p as penny_sample; the mask applies before the top-k / top-p threshold.
+// workspace: as penny_sample.
+PENNY_API int penny_sample_fsm(const void* logits, int is_fp32, long row_stride, const float* temps,
+                               const unsigned long long* seeds, const int* top_k, const float* top_p, int* out,
+                               void* workspace, int B, int V, const int* state, int* state_out,
+                               const unsigned int* masks, int W, int S, const unsigned short* byte_next,
+                               const int* tok_off, const unsigned char* tok_bytes, int nt, const int* done_of,
+                               int eot, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!state || !state_out || !masks || !byte_next || !tok_off || !tok_bytes || !done_of || S <= 0 || nt <= 0 ||
+      eot < 0 || (long)W * 32 < V)
+    return (int)hipErrorInvalidValue;
+  float* pv = (float*)workspace;
+  int* pi = (int*)(pv + (long)B * SAMPLE_SPLITS);
+  const FsmMask fm{state, masks, W, S};
+  float* th = nullptr;
+  if (top_k != nullptr && top_p != nullptr) {
+    th = (float*)(pi + (long)B * SAMPLE_SPLITS);
+    if (is_fp32) {
+      hipLaunchKernelGGL((topk_topp_threshold_kernel<float, true>), dim3(B), dim3(1024), 0, stream,
+                         (const float*)logits, row_stride, temps, top_k, top_p, th, V, fm);
+    } else {
+      hipLaunchKernelGGL((topk_topp_threshold_kernel<bf16, true>), dim3(B), dim3(1024), 0, stream,
+                         (const bf16*)logits, row_stride, temps, top_k, top_p, th, V, fm);
+    }
+  }
+  dim3 grid(B, SAMPLE_SPLITS);
+  if (is_fp32) {
+    hipLaunchKernelGGL((sample_partial_kernel<float, true>), grid, dim3(256), 0, stream, (const float*)logits,
+                       row_stride, temps, seeds, th, pv, pi, V, 0, fm);
+  } else {
+    hipLaunchKernelGGL((sample_partial_kernel<bf16, true>), grid, dim3(256), 0, stream, (const bf16*)logits,
+                       row_stride, temps, seeds, th, pv, pi, V, 0, fm);
+  }
+  const FsmWalk fw{byte_next, tok_off, tok_bytes, done_of, nt, eot};
+  hipLaunchKernelGGL(sample_final_fsm_kernel, dim3(B), dim3(64), 0, stream, pv, pi, out, state, state_out, S, fw);
   PENNY_RETURN_LAUNCH();
 }
 
@@ -344,11 +478,11 @@ PENNY_API int penny_topk_topp_threshold(const void* logits, int is_fp32, long ro
                                         hipStream_t stream) {
   if (B <= 0) return 0;
   if (is_fp32) {
-    hipLaunchKernelGGL(topk_topp_threshold_kernel<float>, dim3(B), dim3(1024), 0, stream, (const float*)logits,
-                       row_stride, temps, top_k, top_p, thresh, V);
+    hipLaunchKernelGGL((topk_topp_threshold_kernel<float, false>), dim3(B), dim3(1024), 0, stream, (const float*)logits,
+                       row_stride, temps, top_k, top_p, thresh, V, FsmMask{});
   } else {
-    hipLaunchKernelGGL(topk_topp_threshold_kernel<bf16>, dim3(B), dim3(1024), 0, stream, (const bf16*)logits,
-                       row_stride, temps, top_k, top_p, thresh, V);
+    hipLaunchKernelGGL((topk_topp_threshold_kernel<bf16, false>), dim3(B), dim3(1024), 0, stream, (const bf16*)logits,
+                       row_stride, temps, top_k, top_p, thresh, V, FsmMask{});
   }
   PENNY_RETURN_LAUNCH();
 }

@@ -16,6 +16,9 @@ alike; ``jump_forward=False`` decodes them one step each.
 Decide calls also decode with prompt-lookup speculation (``engine.speculative``, up to
 ``prompt_lookup`` draft tokens per step): a tool call's arguments mostly copy the user's words.
 
+``constrain_tools`` (off by default): sampled decide calls also carry the tool-call token automaton
+(``agent.automaton``), so every sampled token keeps the output inside the tool-call language.
+
 ``ephemeral_kv`` (agent hint): the prompt carries this turn's tool results, which the next turn
 will not repeat, so its freshly computed KV blocks are recycled before any other cached prefix
 (``PyBlockManager.free``) -- the conversation prefixes that DO recur survive in HBM.
@@ -42,7 +45,8 @@ class EngineLLM(LLMBackend):
                  decide_script: Optional[Callable[[Sequence[ChatMessage], Sequence[Tool]], str]] = None,
                  respond_ignore_eos: bool = False, respond_tokens: Optional[int] = None,
                  stream_chunk_tokens: int = 1, history_token_budget: Optional[int] = None,
-                 jump_forward: bool = True, prompt_lookup: Optional[int] = None):
+                 jump_forward: bool = True, prompt_lookup: Optional[int] = None, constrain_tools: bool = False,
+                 fsm_max_states: Optional[int] = None):
         self.engine = engine
         self.tok = engine.tokenizer
         self.encoder = ChatEncoder(self.tok)
@@ -52,6 +56,10 @@ class EngineLLM(LLMBackend):
         self.prompt_lookup = (int(os.environ.get("PENNY_PROMPT_LOOKUP", "8")) if prompt_lookup is None
                               else prompt_lookup)
         self.decide_script = decide_script
+        # constrained tool-call decoding (agent.automaton): sampled decide outputs stay inside the
+        # tool-call language; off by default (PENNY_CONSTRAIN_TOOLCALLS=1 / ServingConfig)
+        self.constrain_tools = bool(constrain_tools) and self._can_constrain()
+        self.fsm_max_states = fsm_max_states
         self.respond_ignore_eos = respond_ignore_eos
         self.respond_tokens = respond_tokens
         self.stream_chunk_tokens = max(1, stream_chunk_tokens)
@@ -79,6 +87,26 @@ class EngineLLM(LLMBackend):
             if seq.first_token_time is not None:
                 lat["to_first"].append(seq.first_token_time - seq.admit_time)
         lat["total"].append(_t.perf_counter() - seq.arrival)
+
+    def _can_constrain(self) -> bool:
+        """Constraints need the in-process engine at TP = 1 without CP (``LLMEngine.add_request``
+        refuses them otherwise); elsewhere the switch is dropped with one warning."""
+        core = getattr(self.engine, "engine", None)
+        cfg = getattr(core, "cfg", None)
+        if core is None or getattr(cfg, "tp_size", 1) > 1 or getattr(core, "cp", None) is not None:
+            from ..utils.logging import get_logger
+            get_logger(__name__).warning("constrained tool-call decoding needs the in-process engine at TP = 1 "
+                                         "without CP; decide calls decode unconstrained")
+            return False
+        return True
+
+    def _constraint(self, tools):
+        if not self.constrain_tools or not tools or self.decide_script is not None:
+            return None
+        from ..agent.automaton import DEFAULT_MAX_STATES, compile_tool_automaton
+        cap = self.fsm_max_states or getattr(getattr(self.engine.engine, "cfg", None), "fsm_max_states",
+                                             DEFAULT_MAX_STATES)
+        return compile_tool_automaton(tools, self.tok, max_states=cap)
 
     def count_tokens(self, text: str) -> int:
         return self.encoder.count(text)
@@ -113,7 +141,8 @@ class EngineLLM(LLMBackend):
             if grammar is not None:
                 jump = jump_mask(forced, self.tok.decode, grammar, self.eot)
         params = SamplingParams(temperature=temperature, max_tokens=max_tokens, forced_output=forced,
-                                forced_jump=jump, grammar=grammar, ephemeral_kv=bool(kw.get("ephemeral_kv")),
+                                forced_jump=jump, grammar=grammar, constraint=self._constraint(tools),
+                                ephemeral_kv=bool(kw.get("ephemeral_kv")),
                                 prompt_lookup=self.prompt_lookup, priority_ts=TURN_START.get())
         out = await self.engine.generate_all(ids, params)
         self._account(kw.get("purpose", "decide"), len(ids), out.seq)

@@ -95,7 +95,8 @@ class LLMEngine:
                                    short_reserve_tokens=getattr(cfg, "sched_short_reserve_tokens", 0),
                                    short_first=getattr(cfg, "sched_short_first", False))
         self.runner = ModelRunner(self.model, self.kv, cfg.max_model_len, max_decode_batch=cfg.max_num_seqs,
-                                  use_graphs=cfg.use_cuda_graph, graph_sizes=cfg.graph_batch_sizes)
+                                  use_graphs=cfg.use_cuda_graph, graph_sizes=cfg.graph_batch_sizes,
+                                  fsm_max_states=getattr(cfg, "fsm_max_states", 4096))
         self.requests: Dict[str, Sequence] = {}
         self.timing = {"prepare_s": 0.0, "execute_s": 0.0, "post_s": 0.0}   # host-side step anatomy
         self.spec_stats = {"proposed": 0, "accepted": 0}   # prompt-lookup draft tokens
@@ -137,6 +138,14 @@ class LLMEngine:
             raise ValueError("empty prompt")
         max_prompt = self.cfg.max_model_len - 1
         seq = Sequence(request_id, list(prompt_ids)[-max_prompt:], params)
+        if params.constraint is not None:
+            if self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None:
+                raise NotImplementedError("constrained decoding: TP / CP engines do not carry automaton states yet")
+            if params.forced_output is None:       # scripted outputs sample nothing
+                try:
+                    seq.fsm_off = self.runner.register_automaton(params.constraint)
+                except ValueError as e:            # tables full / other tokenizer: decode as before
+                    logger.warning(f"request {request_id}: constraint dropped ({e}); decoding unconstrained")
         self.requests[request_id] = seq
         if self.cp is not None and self.cp.wants(seq):
             self.cp.queue.append(seq)          # prefilled context-parallel before the next step
@@ -303,6 +312,26 @@ class LLMEngine:
                     break
         if draft and p.grammar is not None and p.forced_output is None:
             draft = self._grammar_cut(seq, list(after), draft)
+        if draft and seq.fsm_off is not None and p.forced_output is None:
+            draft = self._fsm_cut(seq, list(after), draft)
+        return draft
+
+    @staticmethod
+    def _fsm_cut(seq: Sequence, after: List[int], draft: List[int]) -> List[int]:
+        """Longest draft prefix the sequence's automaton survives: the constrained sampler can never
+        emit the first token that kills it, so verifying it (and anything behind it) is wasted."""
+        if PENDING in seq.output_ids:
+            return []
+        a = seq.params.constraint
+        s = seq.fsm_state_before(len(seq.output_ids))
+        for t in after:
+            s = a.advance(s, t)
+        if s < 0:                                   # outside the language already: unconstrained rows
+            return draft
+        for k, t in enumerate(draft):
+            s = a.advance(s, t)
+            if s < 0:
+                return draft[:k]
         return draft
 
     def _grammar_cut(self, seq: Sequence, after: List[int], draft: List[int]) -> List[int]:
@@ -676,6 +705,8 @@ class LLMEngine:
     def stats(self) -> Dict[str, float]:
         return {"running": len(self.scheduler.running), "waiting": len(self.scheduler.waiting),
                 "scored_tokens": self.scored_tokens,
+                "constrained_tokens": self.runner.stats["constrained_tokens"],
+                "constrained_steps": self.runner.stats["constrained_steps"],
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),
                 "preemptions": self.scheduler.num_preemptions,

@@ -57,6 +57,10 @@ class StepInputs:
     top_p: np.ndarray               # [S]
     src: Optional[np.ndarray] = None  # [Bd] row of the previous step's sampled vector (-1: ids[] is real)
     pwork: Optional[np.ndarray] = None  # prefill attention work list (filled by the runner): [n, 2] or lean [., 6]
+    # [S] automaton state per sampled row (constrained decoding; None: no row is constrained):
+    # >= 0 an explicit global state, -1 unconstrained, <= -2 carry row (-2 - v) of the previous
+    # step's state_out (the row's last token is still on the device)
+    fsm_state: Optional[np.ndarray] = None
 
     @property
     def num_prefill_tokens(self) -> int:
@@ -64,7 +68,7 @@ class StepInputs:
 
     # -- C4 wire format: one flat byte buffer (no pickling) ------------------------------------
     _ARRAYS = ("ids", "positions", "slots", "cu_q", "ctx_p", "bt_p", "ctx_d", "bt_d", "logits_idx", "temps",
-               "seeds", "top_k", "top_p", "src", "pwork")
+               "seeds", "top_k", "top_p", "src", "pwork", "fsm_state")
 
     def pack(self) -> np.ndarray:
         """[header int64: max_q_len, then (dtype code, rows, cols) per array] + raw array bytes."""
@@ -132,6 +136,16 @@ def sample_rows(seq, n: int) -> int:
     return max(1, min(seq.spec_rows, n))
 
 
+def fsm_code(seq, k: int) -> int:
+    """``StepInputs.fsm_state`` entry of the row that samples output token k of ``seq``."""
+    if seq.fsm_off is None or seq.params.forced_output is not None:
+        return -1
+    if k > 0 and seq.output_ids[k - 1] < 0:          # PENDING: its state is on the device too
+        return -2 - seq.pending_src if seq.pending_src >= 0 else -1
+    s = seq.fsm_state_before(k)
+    return seq.fsm_off + s if s >= 0 else -1
+
+
 def _table(rows: List[List[int]]) -> np.ndarray:
     """Ragged block tables -> zero-padded [len(rows), max len] int32, in one vectorised scatter."""
     lens = np.fromiter((len(r) for r in rows), np.int64, len(rows))
@@ -152,7 +166,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     slot_parts: List[np.ndarray] = []
     cu = [0]
     ctx_p, tables_p = [], []
-    logits_idx, temps, seeds, tk, tp = [], [], [], [], []
+    logits_idx, temps, seeds, tk, tp, fsm = [], [], [], [], [], []
     max_q = 0
     for seq, start, n in batch.prefill:
         np_ = len(seq.prompt_ids)
@@ -178,6 +192,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
                 seeds.append(seq.step_seed_at(k0 + i))
                 tk.append(seq.params.top_k)
                 tp.append(seq.params.top_p)
+                fsm.append(fsm_code(seq, k0 + i))
     Tp = cu[-1]
     ids_d, pos_d, slots_d = [], [], []
     ctx_d, tables_d, src = [], [], []
@@ -198,6 +213,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
         seeds.append(seq.step_seed())
         tk.append(seq.params.top_k)
         tp.append(seq.params.top_p)
+        fsm.append(fsm_code(seq, len(seq.output_ids)))
 
     i32 = lambda x: np.asarray(x, np.int32)  # noqa: E731
     cat = lambda parts, tail: np.concatenate(parts + [i32(tail)]) if parts else i32(tail)  # noqa: E731
@@ -209,7 +225,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     return StepInputs(cat(ids_parts, ids_d), cat(pos_parts, pos_d), cat(slot_parts, slots_d), i32(cu), i32(ctx_p),
                       _table(tables_p), max_q, i32(ctx_d), bt_d, np.asarray(logits_idx, np.int64),
                       np.asarray(temps, np.float32), np.asarray(seeds, np.int64), i32(tk), np.asarray(tp, np.float32),
-                      src_a)
+                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None)
 
 
 def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
@@ -263,14 +279,17 @@ class PendingStep:
 
 
 class _DecodeGraph:
-    def __init__(self, graph, B: int, out: torch.Tensor, fused: bool = False):
+    def __init__(self, graph, B: int, out: torch.Tensor, fused: bool = False,
+                 state_out: Optional[torch.Tensor] = None):
         # fused: the graph samples inside the LM head (no top-k / top-p support)
-        self.graph, self.B, self.out, self.fused = graph, B, out, fused
+        # state_out: the constrained twin's next automaton states (beside ``out``)
+        self.graph, self.B, self.out, self.fused, self.state_out = graph, B, out, fused, state_out
 
 
 class ModelRunner:
     def __init__(self, model, kv: KVCache, max_model_len: int, max_decode_batch: int = 256,
-                 use_graphs: bool = True, graph_sizes: Tuple[int, ...] = (1, 2, 4, 8, 16, 32, 64, 128, 256)):
+                 use_graphs: bool = True, graph_sizes: Tuple[int, ...] = (1, 2, 4, 8, 16, 32, 64, 128, 256),
+                 fsm_max_states: int = 4096):
         self.model = model
         self.kv = kv
         self.device = model.device
@@ -294,11 +313,22 @@ class ModelRunner:
         self.graphs: Dict[int, _DecodeGraph] = {}
         self.graphs_filt: Dict[int, _DecodeGraph] = {}   # top-k / top-p twins of fused buckets (lazy)
         self._filt_failed: set = set()                    # buckets whose filtered twin could not be captured
+        # constrained decoding (ops.constrain): the device automaton tables are allocated at the first
+        # registration, at a fixed capacity -- the decode graphs capture their pointers
+        self.fsm_max_states = int(fsm_max_states)
+        self.fsm: Optional[ops.FsmTables] = None
+        self._fsm_known: Dict[str, int] = {}              # automaton key -> state offset
+        self._fsm_tok_key = None
+        self.last_fsm_state: Optional[torch.Tensor] = None   # state_out of the latest step, beside last_sampled
+        self._step_state_out: Optional[torch.Tensor] = None
+        self.graphs_fsm: Dict[int, _DecodeGraph] = {}     # constrained twins of the decode buckets (lazy)
+        self._fsm_failed: set = set()
         self._static = None
         self.graph_pool = None
         self.stats = {"steps": 0, "graph_steps": 0, "tokens": 0, "prefill_steps": 0, "prefill_step_tokens": 0,
                       "prefill_tile_pad_rows": 0, "prefill_m_hist": [0] * len(PREFILL_M_BUCKETS), "gpu_graph_s": 0.0, "gpu_eager_s": 0.0,
-                      "gpu_idle_s": 0.0, "gpu_idle_gaps": 0, "_prev_end_ev": None, "overlap_steps": 0}
+                      "gpu_idle_s": 0.0, "gpu_idle_gaps": 0, "_prev_end_ev": None, "overlap_steps": 0,
+                      "constrained_steps": 0, "constrained_tokens": 0}
         # TP prefill steps of >= overlap_min_rows rows run as two micro-batches whose all-reduces
         # overlap the other half's compute (PENNY_TP_OVERLAP=0 disables)
         self.tp_overlap = os.environ.get("PENNY_TP_OVERLAP", "1") == "1"
@@ -393,6 +423,33 @@ class ModelRunner:
             m.block_tables_d = self._to_dev(si.bt_d)
         return m
 
+    def register_automaton(self, a) -> int:
+        """Stack a ``TokenAutomaton`` into the device tables (once per automaton) and return the
+        offset of its states: state ids are global, so one step can carry rows of different tool
+        sets.  Raises ValueError when it does not fit ``fsm_max_states`` or was compiled for another
+        tokenizer than the automata already present."""
+        off = self._fsm_known.get(a.key)
+        if off is not None:
+            return off
+        tok_key = (len(a.tok_off), int(a.tok_off[-1]), a.eot_id)
+        if self.fsm is None:
+            self.fsm = ops.FsmTables(self.fsm_max_states, self.model.cfg.vocab_size, a.tok_off, a.tok_bytes,
+                                     a.eot_id, self.device)
+            self._fsm_tok_key = tok_key
+            self.last_fsm_state = torch.full((self.max_samplers,), -1, dtype=torch.int32, device=self.device)
+        elif tok_key != self._fsm_tok_key:
+            raise ValueError("automaton compiled for another tokenizer than the tables hold")
+        off = self.fsm.add(a.byte_next, a.accept, a.done)
+        self._fsm_known[a.key] = off
+        logger.info(f"automaton registered: {a.num_states} states at offset {off} "
+                    f"({self.fsm.used}/{self.fsm.capacity} in use)")
+        return off
+
+    def _resolve_fsm(self, code: torch.Tensor) -> torch.Tensor:
+        """Step-local automaton states: carry codes (<= -2) read the previous step's ``state_out``
+        (``last_fsm_state``) -- before any kernel of this step writes it."""
+        return torch.where(code <= -2, self.last_fsm_state[(-2 - code).clamp(min=0).long()], code)
+
     def _gather_pending(self, ids: torch.Tensor, src: torch.Tensor, offset: int) -> None:
         """ids[offset + r] <- last_sampled[src[r]] where src[r] >= 0 (device-side, no host sync)."""
         rows = ids[offset:offset + src.shape[0]]
@@ -475,8 +532,13 @@ class ModelRunner:
     def logits_and_sample(self, si: StepInputs) -> torch.Tensor:
         """Forward the step, then sample one token per ``si.logits_idx`` row: fused into the LM head
         where it applies (no top-k / top-p rows), else logits -> sampler."""
+        state = None
+        if si.fsm_state is not None:       # resolved where the pending ids are gathered: before any write
+            state = self._resolve_fsm(self._to_dev(si.fsm_state))
         h = self._hidden(si)
         hs = h.index_select(0, self._to_dev(si.logits_idx))
+        if state is not None:              # constrained rows: logits -> masked sampler, as top-k / top-p steps
+            return self.sample(self.model.logits(hs), si, state)
         if not self._has_filters(si) and self._shard_sampling():
             self.stats["vocab_parallel_sample_steps"] = self.stats.get("vocab_parallel_sample_steps", 0) + 1
             return self.model.sample_vocab_parallel(hs, self._to_dev(si.temps), self._to_dev(si.seeds))
@@ -486,9 +548,17 @@ class ModelRunner:
                                       wt=self._lm_tiled())
         return self.sample(self.model.logits(hs), si)
 
-    def sample(self, logits: torch.Tensor, si: StepInputs) -> torch.Tensor:
+    def sample(self, logits: torch.Tensor, si: StepInputs, state: Optional[torch.Tensor] = None) -> torch.Tensor:
         temps = self._to_dev(si.temps)
         seeds = self._to_dev(si.seeds)
+        if state is not None:
+            if self.fsm is None:
+                raise RuntimeError("a constrained step without a registered automaton")
+            filt = self._has_filters(si)
+            out, self._step_state_out = ops.sample_constrained(
+                logits.contiguous(), temps, seeds, state, self.fsm,
+                top_k=self._to_dev(si.top_k) if filt else None, top_p=self._to_dev(si.top_p) if filt else None)
+            return out
         if self._has_filters(si):   # device-side top-k/top-p threshold
             return ops.sample(logits.contiguous(), temps, seeds, top_k=self._to_dev(si.top_k),
                               top_p=self._to_dev(si.top_p))
@@ -550,6 +620,11 @@ class ModelRunner:
                     self._staged = None
         n = len(si.logits_idx)
         self.last_sampled[:n].copy_(out[:n].to(torch.int32), non_blocking=True)
+        if si.fsm_state is not None:
+            so, self._step_state_out = self._step_state_out, None
+            self.last_fsm_state[:n].copy_(so[:n], non_blocking=True)
+            self.stats["constrained_steps"] += 1
+            self.stats["constrained_tokens"] += int((si.fsm_state != -1).sum())
         ar = comm.custom_all_reduce()
         if not self.on_gpu:
             cpu = out[:n].clone()
@@ -603,6 +678,7 @@ class ModelRunner:
             torch.cuda.synchronize(self.device)
         self.graphs.clear()
         self.graphs_filt.clear()
+        self.graphs_fsm.clear()
         self.use_graphs = False
         self._dual = False
 
@@ -615,25 +691,28 @@ class ModelRunner:
         # by ONE pinned H2D copy
         self._src_off = 4 * B + B * W          # pending-token gather rows (-1: host id)
         self._topk_off = self._src_off + B     # per-row top-k (0: off)
-        self._dev_i32 = torch.zeros(self._topk_off + B, dtype=torch.int32, device=self.device)
+        self._fsm_off = self._topk_off + B     # per-row automaton state / carry code (-1: unconstrained)
+        self._dev_i32 = torch.zeros(self._fsm_off + B, dtype=torch.int32, device=self.device)
         d = self._dev_i32
         self._static = {
             "ids": d[0:B], "pos": d[B:2 * B], "slots": d[2 * B:3 * B], "ctx": d[3 * B:4 * B],
             "bt": d[4 * B:self._src_off].view(B, W),
             "src": d[self._src_off:self._topk_off],
             "top_k": d[self._topk_off:self._topk_off + B],
+            "fsm": d[self._fsm_off:self._fsm_off + B],
             "f32": torch.zeros(2 * B, dtype=torch.float32, device=self.device),     # temps | top_p
             "seeds": torch.zeros(B, dtype=torch.int64, device=self.device),
         }
         self._static["slots"].fill_(-1)
         self._static["ctx"].fill_(1)
         self._static["src"].fill_(-1)
+        self._static["fsm"].fill_(-1)
         self._static["temps"], self._static["top_p"] = self._static["f32"][:B], self._static["f32"][B:]
         self._static["top_p"].fill_(1.0)
         # two pinned staging sets, alternated per graph step: in overlap mode the host packs step
         # N+1 while step N's H2D copy may still be queued behind step N-1 on the stream, so a
         # single buffer could be overwritten before the DMA reads it
-        self._pinned_sets = [(torch.zeros(self._topk_off + B, dtype=torch.int32).pin_memory(),
+        self._pinned_sets = [(torch.zeros(self._fsm_off + B, dtype=torch.int32).pin_memory(),
                               torch.zeros(2 * B, dtype=torch.float32).pin_memory(),
                               torch.zeros(B, dtype=torch.int64).pin_memory()) for _ in range(2)]
         self._pin_flip = 0
@@ -661,9 +740,11 @@ class ModelRunner:
                                                          self.device)
         return self._dual
 
-    def _run_static(self, B: int, filtered: bool = False) -> torch.Tensor:
+    def _run_static(self, B: int, filtered: bool = False, fsm: bool = False) -> torch.Tensor:
         s = self._static
         self._gather_pending(s["ids"], s["src"][:B], 0)
+        if fsm:      # carry codes -> states, in place, before the sampler of this graph writes state_out
+            s["fsm"][:B].copy_(self._resolve_fsm(s["fsm"][:B]))
         if self.dual_decode and B >= self.dual_min_batch:
             k = B // 2                       # two chains: rows [0, k) and [k, B)
             metas = [AttentionMetadata(slots=s["slots"][a:b], num_prefill_tokens=0, num_decode=b - a,
@@ -675,6 +756,13 @@ class ModelRunner:
             meta = AttentionMetadata(slots=s["slots"][:B], num_prefill_tokens=0, num_decode=B,
                                      ctx_lens_d=s["ctx"][:B], block_tables_d=s["bt"][:B], decode_ws=self.decode_ws)
             h = self.model.forward(s["ids"][:B], s["pos"][:B], meta, self.kv)
+        if fsm:
+            # the constrained twin: mask, then the top-k / top-p threshold (unfiltered rows leave it
+            # after reading their parameters), then the sampler and the state update
+            out, self._step_state_out = ops.sample_constrained(
+                self.model.logits(h), s["temps"][:B], s["seeds"][:B], s["fsm"][:B], self.fsm,
+                top_k=s["top_k"][:B], top_p=s["top_p"][:B])
+            return out
         if not filtered:
             if self._shard_sampling():     # TP: top-k / top-p rows of this bucket replay eagerly
                 return self.model.sample_vocab_parallel(h, s["temps"][:B], s["seeds"][:B])
@@ -709,51 +797,62 @@ class ModelRunner:
         logger.info(f"captured decode hipGraphs for batch sizes {sorted(self.graphs)}")
 
     def _fused_graph_needs_eager(self, si: StepInputs) -> bool:
-        """A decode step with top-k / top-p rows whose bucket's graph samples inside the LM head: at
-        TP=1 it replays the bucket's FILTERED twin (logits -> threshold -> sampler), captured on the
-        first such step; under TP (vocab-parallel candidates) it runs eagerly."""
-        if not self._has_filters(si):
+        """A decode step its bucket's graph cannot sample: top-k / top-p rows when the graph samples
+        inside the LM head, or constrained rows (any graph).  At TP=1 it replays the bucket's TWIN
+        (filtered: logits -> threshold -> sampler; constrained: logits -> masked threshold -> masked
+        sampler + state update), captured on the first such step; under TP it runs eagerly."""
+        fsm = si.fsm_state is not None
+        if not fsm and not self._has_filters(si):
             return False
         if not self.graphs:
             self.capture_graphs()
         B = self._bucket(si.num_decode)
         G = self.graphs.get(B)
-        if G is None or not G.fused:
+        if G is None or not (G.fused or fsm):
             return False
         if getattr(self.model, "tp_size", 1) > 1:
             return True
-        if B in self._filt_failed:
+        twins, failed = (self.graphs_fsm, self._fsm_failed) if fsm else (self.graphs_filt, self._filt_failed)
+        if B in failed:
             return True
-        if B not in self.graphs_filt:
+        if B not in twins:
             try:
-                self._capture_filtered(B)
+                self._capture_twin(B, fsm)
             except Exception as e:  # noqa: BLE001 - e.g. out of memory after the KV pool took HBM
-                # (ADVICE r5): this bucket's filtered rows stay on the eager path for good
-                logger.warning(f"filtered decode graph for batch {B} not captured ({e}); running it eagerly")
-                self._filt_failed.add(B)
+                # (ADVICE r5): this bucket's filtered / constrained rows stay on the eager path for good
+                kind = "constrained" if fsm else "filtered"
+                logger.warning(f"{kind} decode graph for batch {B} not captured ({e}); running it eagerly")
+                failed.add(B)
                 torch.cuda.synchronize(self.device)
                 return True
         return False
 
-    def _capture_filtered(self, B: int) -> None:
+    def _capture_twin(self, B: int, fsm: bool) -> None:
         """Capture mid-serving: the static inputs still hold the step in flight, so the warm-up and
-        capture passes run with every KV slot masked (< 0: no cache write) and no pending-token
-        gather -- they must not rewrite live sequences' KV -- and the inputs are restored after."""
+        capture passes run with every KV slot masked (< 0: no cache write), no pending-token
+        gather and no automaton state -- they must not rewrite live sequences' KV -- and the inputs
+        are restored after."""
         s = self._static
-        saved = (s["slots"][:B].clone(), s["src"][:B].clone())
+        saved = (s["slots"][:B].clone(), s["src"][:B].clone(), s["fsm"][:B].clone())
         s["slots"][:B].fill_(-1)
         s["src"][:B].fill_(-1)
+        s["fsm"][:B].fill_(-1)
         try:
             for _ in range(2):
-                self._run_static(B, filtered=True)
+                self._run_static(B, filtered=True, fsm=fsm)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self.graph_pool):
-                out = self._run_static(B, filtered=True)
-            self.graphs_filt[B] = _DecodeGraph(g, B, out, False)
+                out = self._run_static(B, filtered=True, fsm=fsm)
+            if fsm:
+                self.graphs_fsm[B] = _DecodeGraph(g, B, out, False, self._step_state_out)
+            else:
+                self.graphs_filt[B] = _DecodeGraph(g, B, out, False)
         finally:                                  # the step in flight keeps its inputs either way
+            self._step_state_out = None
             s["slots"][:B].copy_(saved[0])
             s["src"][:B].copy_(saved[1])
+            s["fsm"][:B].copy_(saved[2])
             torch.cuda.synchronize()
 
     def _bucket(self, n: int) -> int:
@@ -768,7 +867,9 @@ class ModelRunner:
         n = si.num_decode
         B = self._bucket(n)
         G = self.graphs[B]
-        if G.fused and self._has_filters(si) and B in self.graphs_filt:
+        if si.fsm_state is not None:
+            G = self.graphs_fsm[B]
+        elif G.fused and self._has_filters(si) and B in self.graphs_filt:
             G = self.graphs_filt[B]
         S, W = self.max_decode_batch, self.max_blocks
         self._pinned_i32, self._pinned_f, self._pinned_l = self._pinned_sets[self._pin_flip]
@@ -791,6 +892,10 @@ class ModelRunner:
         tk = buf[self._topk_off:self._topk_off + S]
         tk[:B] = 0
         tk[:n] = si.top_k
+        fs = buf[self._fsm_off:self._fsm_off + S]
+        fs[:B] = -1
+        if si.fsm_state is not None:
+            fs[:n] = si.fsm_state
         f = self._pinned_f.numpy()
         f[:n] = si.temps
         f[S:S + B] = 1.0
@@ -802,4 +907,5 @@ class ModelRunner:
         s["seeds"].copy_(self._pinned_l, non_blocking=True)
         G.graph.replay()
         self.stats["graph_steps"] += 1
+        self._step_state_out = G.state_out
         return G.out[:n]

@@ -38,6 +38,10 @@ class SamplingParams:
     # from the prompt are verified per step (0 = off)
     prompt_lookup: int = 0
     priority_ts: Optional[float] = None   # scheduling time (TURN_START); None: the request's arrival
+    # constrained decoding (agent.automaton.TokenAutomaton): every SAMPLED token keeps the output
+    # inside the automaton's language (the device sampler masks the rest); teacher-forced outputs
+    # (forced_output) sample nothing and ignore it.  TP = 1 without CP only.
+    constraint: Optional[object] = None
 
 
 class SeqStatus(enum.Enum):
@@ -87,6 +91,30 @@ class Sequence:
         self.spec_lookup = None
         self.spec_proposed = 0
         self.spec_accepted = 0
+        # constrained decoding: fsm_off -- offset of the request's automaton in the runner's device
+        # tables (None: unconstrained); (fsm_pos, fsm_state) -- the host mirror: the automaton's local
+        # state after the first fsm_pos output tokens (never past an unverified draft token)
+        self.fsm_off: Optional[int] = None
+        self.fsm_pos = 0
+        self.fsm_state = 0
+
+    def fsm_state_before(self, k: int) -> int:
+        """Local automaton state in front of output token k (every earlier token known; -1: the
+        output left the language, the row goes on unconstrained).  Advances the mirror over tokens
+        that will not be taken back (a prompt-lookup draft in the tail may be)."""
+        a = self.params.constraint
+        if k < self.fsm_pos:
+            self.fsm_pos, self.fsm_state = 0, a.start
+        elif self.fsm_pos == 0:
+            self.fsm_state = a.start
+        stable = len(self.output_ids) - max(self.spec_rows - 1, 0)
+        s = self.fsm_state
+        out = self.output_ids
+        for i in range(self.fsm_pos, k):
+            s = a.advance(s, out[i])
+            if i < stable:
+                self.fsm_pos, self.fsm_state = i + 1, s
+        return s
 
     def drop_draft(self) -> None:
         """Forget a prompt-lookup draft that was appended but never launched (preemption)."""

@@ -61,7 +61,8 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
         store.load_synthetic(retrieval_cfg.corpus_size, retrieval_cfg.num_users)
     retrieval = RetrievalService(embedder, store)
     llm = EngineLLM(engine, max_model_len=engine_cfg.max_model_len,
-                    history_token_budget=serving.history_token_budget)
+                    history_token_budget=serving.history_token_budget,
+                    constrain_tools=serving.constrain_toolcalls, fsm_max_states=engine_cfg.fsm_max_states)
     if not serving.tools:
         agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens)
     else:

@@ -44,6 +44,9 @@ def parse(argv=None):
     ap.add_argument("--tool-steps", type=int, default=1, help=">1 enables the multi-step agent (retrieval + plot)")
     ap.add_argument("--no-tools", action="store_true",
                     help="legacy single-chain chat (llm_service.py): no decide step, no retrieval")
+    ap.add_argument("--constrain-toolcalls", action="store_true",
+                    default=os.environ.get("PENNY_CONSTRAIN_TOOLCALLS", "0").lower() in ("1", "true", "yes"),
+                    help="decide calls sample under the tool-call token automaton (TP = 1 only)")
     ap.add_argument("--max-model-len", type=int, default=8192)
     ap.add_argument("--device", default=None)
     ap.add_argument("--no-http", action="store_true")
@@ -71,7 +74,9 @@ def build_leader_services(args, engine, device):
         store = NumpyVectorStore(768)
     retrieval = RetrievalService(embedder, store)
     serving = config.ServingConfig.from_env()
-    llm = EngineLLM(engine, max_model_len=args.max_model_len, history_token_budget=serving.history_token_budget)
+    llm = EngineLLM(engine, max_model_len=args.max_model_len, history_token_budget=serving.history_token_budget,
+                    constrain_tools=args.constrain_toolcalls or serving.constrain_toolcalls,
+                    fsm_max_states=config.EngineConfig.from_env().fsm_max_states)
     if args.no_tools or not serving.tools:
         agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens)
     else:

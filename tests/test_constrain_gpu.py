@@ -1,0 +1,423 @@
+"""Constrained tool-call decoding on the GPU: the mask-build kernel against the numpy oracle bit for
+bit, ``ops.sample_constrained`` against the fp64 replica of the sampler (``selection_ref``) fed the
+logits with -inf at disallowed tokens, the device state carry, and the engine end to end (eager,
+hipGraph, overlap and synchronous stepping).
+"""
+import json
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from constrain_ref import check_output
+from financial_chatbot_llm_amd import ops
+from financial_chatbot_llm_amd.agent.automaton import DEAD, build_masks_ref, compile_tool_automaton, mask_words
+from financial_chatbot_llm_amd.config import EngineConfig
+from financial_chatbot_llm_amd.engine import LLMEngine, SamplingParams
+from financial_chatbot_llm_amd.engine.model_runner import ModelRunner
+from financial_chatbot_llm_amd.engine.tokenizer import SyntheticLlamaTokenizer
+from financial_chatbot_llm_amd.tools import make_plot_tool, make_retrieval_tool
+from selection_ref import check_sampled, sample_ref
+from test_constrain_cpu import PROBE
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+# the sampler tests' score tolerance (tests/test_selection_kernels_gpu.py: 16 x the float32 floor of
+# the score formula over N(0, 9) logits at V = 128256; the inputs here are drawn the same way)
+EPS = 16 * 1.46e-6
+TEMPS = [0.5, 1.0, 2.0, 0.0, 2.0, 0.0, 1.0, 0.5]
+
+
+def synthetic_fsm(V: int, S: int, seed: int):
+    """A hand-made automaton over the letters a-h and V tokens of 0-5 letters: token 0..7 are the
+    single letters, every 7th token and the last three have no bytes, eot = V - 3, done = S - 1."""
+    rng = np.random.default_rng(seed)
+    pieces = []
+    for t in range(V):
+        if t < 8:
+            pieces.append(bytes([97 + t]))
+        elif t % 7 == 0 or t >= V - 3:
+            pieces.append(b"")
+        else:
+            pieces.append(bytes(rng.integers(97, 105, rng.integers(1, 6)).tolist()))
+    off = np.zeros(V + 1, np.int32)
+    np.cumsum([len(p) for p in pieces], out=off[1:])
+    data = np.frombuffer(b"".join(pieces), np.uint8).copy()
+    nxt = np.full((S, 256), DEAD, np.uint16)
+    for s in range(S - 2):                           # S - 2: a state without edges, S - 1: done
+        for b in range(97, 105):
+            if rng.random() < 0.7:
+                nxt[s, b] = rng.integers(0, S - 1)
+    accept = (rng.random(S) < 0.4).astype(np.uint8)
+    accept[S - 1] = 1
+    accept[S - 2] = 0                                # admits nothing at all
+    return nxt, accept, off, data, V - 3
+
+
+@pytest.fixture(scope="module")
+def tok():
+    return SyntheticLlamaTokenizer()
+
+
+@pytest.fixture(scope="module")
+def real(tok):
+    """The two-tool automaton in device tables, behind 3 states of padding (a nonzero offset)."""
+    a = compile_tool_automaton([make_retrieval_tool(None), make_plot_tool()], tok)
+    t = ops.FsmTables(4096, a.vocab_size, a.tok_off, a.tok_bytes, a.eot_id, DEV)
+    t.used = 3
+    off = t.add(a.byte_next, a.accept, a.done)
+    assert off == 3
+    return a, t, off
+
+
+def small_tables(V=1005, S=12, seed=4, dev=DEV):
+    nxt, accept, off, data, eot = synthetic_fsm(V, S, seed)
+    t = ops.FsmTables(S + 5, V, off, data, eot, dev)
+    assert t.add(nxt, accept, S - 1) == 0
+    return t
+
+
+def host_walk(t, st: int, tok_id: int) -> int:
+    """Independent host replica of the state update for an allowed token."""
+    if st < 0:
+        return -1
+    if tok_id == t.eot:
+        return int(t.h_done_of[st])
+    for b in t.h_tok_bytes[t.h_tok_off[tok_id]:t.h_tok_off[tok_id + 1]].tolist():
+        st = int(t.h_byte_next[st, b])
+        assert st != DEAD
+    return st
+
+
+# ---------------------------------------------------------------------------------------------
+# 5. the mask-build kernel
+# ---------------------------------------------------------------------------------------------
+def test_mask_build_hand_made_v70():
+    """V = 70: two ballot groups, the second with 6 live lanes; 3 mask words rounded up to 4."""
+    nxt, accept, off, data, eot = synthetic_fsm(70, 9, seed=1)
+    t = ops.FsmTables(16, 70, off, data, eot, DEV)
+    assert t.W == 4 == mask_words(70)
+    t.masks.fill_(-1)                                # stale bits must be overwritten, tails zeroed
+    assert t.add(nxt, accept, 8) == 0
+    got = t.masks.cpu().numpy().view(np.uint32)
+    want = build_masks_ref(nxt, accept, off, data, eot)
+    assert np.array_equal(got[:9], want)
+    assert (got[9:] == 0xFFFFFFFF).all()             # rows outside the range are not touched
+    assert (want[:, 2] >> 6 == 0).all() and (want[:, 3] == 0).all()      # bits at or beyond V
+    assert want.any() and (want[7] == 0).all()       # the edgeless state admits nothing
+    # a second automaton stacked behind the first: global state ids in the transitions
+    g = nxt[:7].copy()
+    g[g >= 7] = DEAD
+    t2 = ops.FsmTables(16, 70, off, data, eot, DEV)
+    t2.used = 9
+    t2.add(g, accept[:7], 6)
+    want2 = build_masks_ref(g, accept[:7], off, data, eot)
+    assert np.array_equal(t2.masks.cpu().numpy().view(np.uint32)[9:16], want2)
+
+
+def test_mask_build_real_two_tool_automaton(real):
+    a, t, off = real
+    got = t.masks.cpu().numpy().view(np.uint32)
+    want = a.masks()
+    assert want.shape == (a.num_states, mask_words(128256))
+    assert np.array_equal(got[off:off + a.num_states], want)
+    assert not got[:off].any() and not got[off + a.num_states:].any()
+
+
+# ---------------------------------------------------------------------------------------------
+# 6. sample_constrained against the fp64 replica
+# ---------------------------------------------------------------------------------------------
+def allowed_bits(t, states, V):
+    masks = t.masks.cpu().numpy().view(np.uint32)
+    out = np.ones((len(states), V), bool)
+    for r, s in enumerate(states):
+        if s >= 0:
+            out[r] = np.unpackbits(masks[s].view(np.uint8), bitorder="little")[:V].astype(bool)
+    return out
+
+
+def case(B, V, dtype, t, live_states, done_state, dead_state):
+    g = torch.Generator().manual_seed(17 * B + V)
+    logits = (torch.randn(B, V, generator=g) * 3.0).to(dtype)
+    temps = torch.tensor((TEMPS * 8)[:B])
+    seeds = torch.arange(B, dtype=torch.int64) * 7919 + 5 + 1000003 * V
+    rng = np.random.default_rng(B + V)
+    states = rng.choice(live_states, B).tolist()
+    for r in range(B):                               # unconstrained, done and empty-mask rows mixed in
+        if r % 5 == 1:
+            states[r] = -1
+        elif r % 11 == 4:
+            states[r] = done_state
+        elif r % 13 == 7:
+            states[r] = dead_state
+    return logits, temps, seeds, states
+
+
+def run_case(B, V, dtype, t, live_states, done_state, dead_state, top=None):
+    logits, temps, seeds, states = case(B, V, dtype, t, live_states, done_state, dead_state)
+    allow = allowed_bits(t, states, V)
+    masked = logits.float().clone()
+    masked[torch.from_numpy(~allow)] = float("-inf")
+    keep = None
+    kw = {}
+    if top is not None:
+        k, p = top(masked, temps)
+        keep = torch.isfinite(ops.apply_top_k_top_p(masked, k, p, temps)) & torch.from_numpy(allow)
+        kw = dict(top_k=k.to(DEV), top_p=p.to(DEV))
+    st = torch.tensor(states, dtype=torch.int32, device=DEV)
+    tok_d, ns_d = ops.sample_constrained(logits.to(DEV), temps.to(DEV), seeds.to(DEV), st, t, **kw)
+    tok_ids, ns = tok_d.cpu().tolist(), ns_d.cpu().tolist()
+    empty = ~allow.any(1)
+    rows = np.flatnonzero(~empty)
+    scores, _, _ = sample_ref(masked, temps, seeds, keep=keep)
+    check_sampled(np.asarray(tok_ids)[rows], scores[rows], EPS, greedy=(temps <= 0).numpy()[rows])
+    for r in range(B):
+        if empty[r]:
+            assert tok_ids[r] == t.eot and ns[r] == int(t.h_done_of[states[r]]), r
+        else:
+            assert allow[r, tok_ids[r]], r
+            assert ns[r] == host_walk(t, states[r], tok_ids[r]), r
+    return tok_ids, ns, states, allow
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("B", [1, 5, 64])
+def test_sample_constrained_v1005(B, dtype):
+    """V = 1005: 125 chunks + a 5-token tail, the row copied to an aligned buffer."""
+    t = small_tables()
+    live = [s for s in range(10) if allowed_bits(t, [s], 1005).any()]
+    tok_ids, ns, states, allow = run_case(B, 1005, dtype, t, live, 11, 10)
+    if B == 64:
+        assert (~allow.any(1)).sum() >= 3 and sum(s == -1 for s in states) >= 10
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("B", [1, 5, 64])
+def test_sample_constrained_v128256(real, B, dtype):
+    a, t, off = real
+    rng = np.random.default_rng(9)
+    body = off + a.walk(a.start, b'{"name": "retrieve_transactions", "parameters": {"search_query": "x')
+    live = [off + a.start, body] + (off + rng.choice(a.num_states - 3, 24, replace=False) + 3).tolist()
+    live = [s for s in live if s != off + a.done]
+    tok_ids, ns, states, allow = run_case(B, 128256, dtype, t, live, off + a.done, 4000)
+    for r in range(B):                               # the automaton's own walk agrees with the device
+        if 0 <= states[r] < 4000 and allow[r].any():
+            assert ns[r] == off + a.advance(states[r] - off, tok_ids[r]), r
+
+
+@pytest.mark.parametrize("V", [1005, 128256])
+def test_unconstrained_rows_equal_sample_bitwise(real, V):
+    t = real[1] if V == 128256 else small_tables()
+    for dtype in (torch.float32, torch.bfloat16):
+        logits, temps, seeds, _ = case(64, V, dtype, t, [0], 0, 0)
+        d = [x.to(DEV) for x in (logits, temps, seeds)]
+        st = torch.full((64,), -1, dtype=torch.int32, device=DEV)
+        tok_c, ns = ops.sample_constrained(*d, st, t)
+        assert torch.equal(tok_c, ops.sample(*d)) and (ns == -1).all()
+        k = torch.full((64,), 40, dtype=torch.int32, device=DEV)
+        p = torch.full((64,), 0.9, dtype=torch.float32, device=DEV)
+        tok_f, _ = ops.sample_constrained(*d, st, t, top_k=k, top_p=p)
+        assert torch.equal(tok_f, ops.sample(*d, top_k=k, top_p=p))
+
+
+def test_mask_applies_before_top_k_top_p():
+    """fp32 logits (no ties).  top-k: the k-th largest ALLOWED logit is exact whatever it is.  top-p:
+    p sits in the middle of the probability of the last kept token, so the nucleus edge is clear of
+    every rounding (the margin is half that token's mass, > 1e-3)."""
+    t = small_tables()
+    V = 1005
+    live = [s for s in range(10) if allowed_bits(t, [s], V).sum() >= 40]
+    assert live
+
+    def top(masked, temps):
+        B = masked.shape[0]
+        k = torch.zeros(B, dtype=torch.int32)
+        p = torch.ones(B, dtype=torch.float32)
+        for r in range(B):
+            row = masked[r].double()
+            n_ok = int(torch.isfinite(row).sum())
+            if temps[r] <= 0 or n_ok == 0:
+                continue
+            if r % 2 == 0:
+                k[r] = max(1, min(n_ok, 1 + r % 7))
+            else:
+                pr = torch.softmax(torch.sort(row, descending=True).values / float(temps[r]), 0)
+                j = next((j for j in range(6) if pr[j] > 4e-3), None)
+                if j is not None:
+                    p[r] = float(pr[:j].sum() + pr[j] / 2)
+        return k, p
+
+    tok_ids, ns, states, allow = run_case(64, V, torch.float32, t, live, 11, 10, top=top)
+    # the order matters on these inputs: a cut taken over ALL tokens first leaves some rows nothing allowed
+    logits, temps, seeds, states = case(64, V, torch.float32, t, live, 11, 10)
+    k, p = top(torch.where(torch.from_numpy(allow), logits, torch.tensor(float("-inf"))), temps)
+    wrong = torch.isfinite(ops.apply_top_k_top_p(logits, k, p, temps)) & torch.from_numpy(allow)
+    assert (~wrong.any(1) & torch.from_numpy(allow.any(1))).any()
+
+
+def test_all_zero_mask_row_returns_eot(real):
+    a, t, off = real
+    V = 128256
+    logits = torch.randn(3, V, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16).to(DEV)
+    temps = torch.tensor([0.0, 1.0, 1.0], device=DEV)
+    seeds = torch.tensor([1, 2, 3], dtype=torch.int64, device=DEV)
+    st = torch.tensor([4000, 4090, 1], dtype=torch.int32, device=DEV)      # unused states: all-zero masks
+    assert not t.masks[[4000, 4090, 1]].any()
+    k = torch.tensor([0, 5, 0], dtype=torch.int32, device=DEV)
+    p = torch.tensor([1.0, 0.5, 1.0], device=DEV)
+    for kw in ({}, dict(top_k=k, top_p=p)):
+        tok_d, ns = ops.sample_constrained(logits, temps, seeds, st, t, **kw)
+        assert tok_d.tolist() == [a.eot_id] * 3 and ns.tolist() == [4000, 4090, 1]   # done_of an unused state: itself
+
+
+# ---------------------------------------------------------------------------------------------
+# 7. state carry through aliased buffers
+# ---------------------------------------------------------------------------------------------
+def test_state_carry_equals_explicit_states(real):
+    a, t, off = real
+    B, V, steps = 5, 128256, 6
+    g = torch.Generator().manual_seed(23)
+    logits = [(torch.randn(B, V, generator=g) * 3.0).to(torch.bfloat16).to(DEV) for _ in range(steps)]
+    temps = torch.tensor([1.0, 0.0, 1.0, 0.5, 2.0], device=DEV)
+    perm = [3, 0, 4, 1, 2]                           # row r of step n+1 continues row perm[r] of step n
+    start = [off + a.start, -1, off + a.start, off + a.start, off + a.start]
+
+    def seeds(n):
+        return (torch.arange(B, dtype=torch.int64) * 31 + 1000 * n + 7).to(DEV)
+
+    # explicit host states
+    host, toks_h = list(start), []
+    for n in range(steps):
+        st = torch.tensor(host, dtype=torch.int32, device=DEV)
+        tok_d, ns = ops.sample_constrained(logits[n], temps, seeds(n), st, t)
+        ids = tok_d.tolist()
+        toks_h.append(ids)
+        nxt = [off + a.advance(host[r] - off, ids[r]) if host[r] >= 0 else -1 for r in range(B)]
+        assert ns.tolist() == nxt
+        host = [nxt[perm[r]] for r in range(B)]
+    # carry codes: the states never leave the device; state_out aliases the state buffer, which is
+    # then copied to last_fsm_state as the runner does
+    runner = SimpleNamespace(last_fsm_state=torch.full((64,), -1, dtype=torch.int32, device=DEV))
+    codes = torch.tensor(start, dtype=torch.int32, device=DEV)
+    toks_d = []
+    for n in range(steps):
+        st = ModelRunner._resolve_fsm(runner, codes)
+        tok_d, ns = ops.sample_constrained(logits[n], temps, seeds(n), st, t, state_out=st)
+        assert ns.data_ptr() == st.data_ptr()
+        runner.last_fsm_state[:B].copy_(ns)
+        toks_d.append(tok_d.tolist())
+        codes = torch.tensor([-2 - perm[r] for r in range(B)], dtype=torch.int32, device=DEV)
+    assert toks_d == toks_h
+    assert any(len(set(step)) > 1 for step in toks_h)
+
+
+# ---------------------------------------------------------------------------------------------
+# 8. the engine on the GPU
+# ---------------------------------------------------------------------------------------------
+def _engine_run(tok, graph, overlap, model=None):
+    a = compile_tool_automaton([PROBE], tok)
+    # one graph bucket per batch size: graph and eager steps run the same GEMM shapes
+    cfg = EngineConfig(model="llama-tiny", device="cuda", num_kv_blocks=128, max_model_len=1024, max_num_seqs=8,
+                       graph_batch_sizes=(1, 2, 3, 4, 5, 6, 7, 8), use_cuda_graph=graph, async_scheduling=overlap,
+                       seed=0)
+    eng = LLMEngine(cfg, model=model)
+    if graph:
+        eng.warmup()
+    n = 32
+    seqs = [eng.add_request(f"r{i}", list(range(300 + 7 * i, 340 + 7 * i)),
+                            SamplingParams(temperature=1.0, max_tokens=96, seed=1000 + i, constraint=a))
+            for i in range(n)]
+    while any(not s.finished for s in seqs) or eng.has_work():
+        eng.step()
+    eot = tok.special["<|eot_id|>"]
+    for s in seqs:
+        text = tok.decode_bytes([x for x in s.output_ids if x != eot]).decode("utf-8", "surrogateescape")
+        assert s.finish_reason == "stop" and s.output_ids[-1] == eot, (s.finish_reason, text)
+        check_output(text, [PROBE])
+        if text != "No tool call":
+            PROBE.validate(json.loads(text)["parameters"])
+    return [list(s.output_ids) for s in seqs], eng
+
+
+def test_engine_constrained_eager_graph_overlap_sync(tok):
+    eager, e0 = _engine_run(tok, graph=False, overlap=True)
+    assert e0.stats()["constrained_steps"] > 0 and e0.runner.stats["graph_steps"] == 0
+    graph, e1 = _engine_run(tok, graph=True, overlap=True, model=e0.model)
+    assert e1.runner.graphs_fsm and not e1.runner._fsm_failed and e1.runner.stats["graph_steps"] > 0
+    sync, e2 = _engine_run(tok, graph=False, overlap=False, model=e0.model)
+    same_g = sum(x == y for x, y in zip(eager, graph))
+    same_s = sum(x == y for x, y in zip(eager, sync))
+    print(f"constrained engine: graph == eager on {same_g}/32 sequences, sync == overlap on {same_s}/32")
+    assert graph == eager
+    assert sync == eager
+    assert len({tuple(x) for x in eager}) > 8
+
+
+def _gen(eng, tok, params, prompts):
+    seqs = [eng.add_request(f"q{i}-{id(params)}", p, sp) for i, (p, sp) in enumerate(zip(prompts, params))]
+    while any(not s.finished for s in seqs) or eng.has_work():
+        eng.step()
+    eot = tok.special["<|eot_id|>"]
+    texts = [tok.decode_bytes([x for x in s.output_ids if x != eot]).decode("utf-8", "surrogateescape") for s in seqs]
+    return seqs, texts
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+def test_engine_retrieval_tool_jump_forward_and_batch_mates(tok, graph, monkeypatch):
+    """The retrieval tool's strings may run to max_tokens: every output is a viable prefix, every
+    stop-finished one fully valid.  Jump-forward on top saves steps.  Unconstrained batch mates emit
+    the tokens they emit alone; both runs take logits + sampler (PENNY_FUSED_LM_HEAD=0), because the
+    fused LM head and the library GEMM round logits differently (ops.sampling.lm_head_sample)."""
+    from constrain_ref import complete_prefix
+    from financial_chatbot_llm_amd.agent.grammar import ToolCallGrammar
+    monkeypatch.setenv("PENNY_FUSED_LM_HEAD", "0")
+    ret = make_retrieval_tool(None)
+    a = compile_tool_automaton([ret], tok)
+    cfg = EngineConfig(model="llama-tiny", device="cuda", num_kv_blocks=128, max_model_len=1024, max_num_seqs=8,
+                       graph_batch_sizes=(1, 2, 3, 4, 5, 6, 7, 8), use_cuda_graph=graph, seed=0)
+    eng = LLMEngine(cfg)
+    if graph:
+        eng.warmup()
+    n = 6
+    prompts = [list(range(300 + 7 * i, 340 + 7 * i)) for i in range(n + 2)]
+    # short batch mates: the constrained sequences decide how many steps a run takes
+    free = [SamplingParams(temperature=1.0, max_tokens=6, seed=50 + i, ignore_eos=True) for i in range(2)]
+    alone, _ = _gen(eng, tok, free, prompts[n:])
+    for jump in (False, True):
+        g = ToolCallGrammar([ret]) if jump else None
+        con = [SamplingParams(temperature=1.0, max_tokens=40, seed=2000 + i, constraint=a, grammar=g)
+               for i in range(n)]
+        s0, c0 = eng.runner.stats["steps"], eng.runner.stats["constrained_tokens"]
+        seqs, texts = _gen(eng, tok, con + free, prompts)
+        steps, rows = eng.runner.stats["steps"] - s0, eng.runner.stats["constrained_tokens"] - c0
+        for s, text in zip(seqs[:n], texts[:n]):
+            assert a.viable(text.encode("utf-8", "surrogateescape")), text
+            check_output(complete_prefix(text, [ret]), [ret])
+            if s.finish_reason == "stop":
+                check_output(text, [ret])
+        same = sum(x.output_ids == y.output_ids for x, y in zip(seqs[n:], alone))
+        print(f"graph={graph} jump={jump}: {steps} steps, {rows} constrained rows, batch mates equal on {same}/2, "
+              f"{sum(s.finish_reason == 'stop' for s in seqs[:n])}/{n} stopped")
+        assert same == 2
+        if jump:                                     # forced runs are appended, not sampled
+            assert steps < plain[0] and rows < plain[1]
+        plain = (steps, rows)
+
+
+def test_engine_switch_off_keeps_fused_lm_head_steps(tok):
+    """Without a constraint: no constrained step, no table, and every sampling step of a scripted
+    run is a fused LM-head step (eager) -- the dispatch of the parent."""
+    eot = tok.special["<|eot_id|>"]
+    forced = tok.encode('{"name": "probe", "parameters": {"count": 1, "flag": true}}', allow_special=False) + [eot]
+    cfg = EngineConfig(model="llama-tiny", device="cuda", num_kv_blocks=64, max_model_len=1024, max_num_seqs=8,
+                       use_cuda_graph=False, seed=0)
+    eng = LLMEngine(cfg)
+    sampling_steps = []
+    launch = eng.runner.launch
+    eng.runner.launch = lambda si: (sampling_steps.append(len(si.logits_idx) > 0), launch(si))[1]
+    out = eng.generate([list(range(300, 380))], SamplingParams(temperature=0.5, max_tokens=64, forced_output=forced))
+    assert out[0] == forced
+    st = eng.runner.stats
+    assert st["constrained_steps"] == 0 and eng.runner.fsm is None and eng.runner.last_fsm_state is None
+    assert st.get("fused_lm_head_steps", 0) == sum(sampling_steps) > 0
