@@ -36,11 +36,20 @@ __global__ void __launch_bounds__(1024) moe_route_kernel(const bf16* __restrict_
   for (int t = threadIdx.x; t < T; t += blockDim.x) {
     float p[64];
     float mx = -INFINITY;
+    bool poisoned = false;
     for (int e = 0; e < E; ++e) {
       p[e] = (float)logits[(long)t * E + e];
       mx = fmaxf(mx, p[e]);
+      poisoned |= p[e] != p[e];
     }
+    // a row with a NaN, a +inf (mx = +inf) or nothing but -inf (mx = -inf) has a NaN numerator:
+    // route it like an all-equal row (numerators 0: experts 0..K-1, every compare on finite
+    // numbers) with NaN weights
+    poisoned |= !(fabsf(mx) < INFINITY);
     for (int e = 0; e < E; ++e) p[e] = __expf(p[e] - mx);
+    if (poisoned)
+      for (int e = 0; e < E; ++e)
+        if (!(p[e] >= 0.f)) p[e] = 0.f;
     float ws = 0.f;
     for (int j = 0; j < K; ++j) {
       int best = 0;
@@ -52,6 +61,7 @@ __global__ void __launch_bounds__(1024) moe_route_kernel(const bf16* __restrict_
       ws += p[best];
       p[best] = -1.f;
     }
+    if (poisoned) ws = NAN;
     for (int j = 0; j < K; ++j) pw[t * K + j] /= ws;
   }
   __syncthreads();
@@ -100,6 +110,13 @@ __global__ void __launch_bounds__(256) moe_route_quant_kernel(const bf16* __rest
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     float p = lane < E ? __expf(l - mx) : -1.f;
+    // a NaN, a +inf or nothing but -inf in the row leaves a NaN numerator, and a NaN in the arg-max
+    // compares makes the lanes disagree on the winner (slots stored twice, never, or with lane id
+    // E).  Such a row is routed like an all-equal one (numerators 0: experts 0..K-1, every lane
+    // comparing finite numbers) and its weights are NaN, so the token's output row is NaN
+    const bool bad = lane < E && !(p >= 0.f);
+    const bool poisoned = __ballot(bad) != 0;
+    if (bad) p = 0.f;
     float ws = 0.f, mine = 0.f;
     int myj = -1;
     for (int j = 0; j < K; ++j) {
@@ -116,7 +133,7 @@ __global__ void __launch_bounds__(256) moe_route_quant_kernel(const bf16* __rest
     }
     if (myj >= 0) {
       pe[t * K + myj] = lane;
-      pw[t * K + myj] = mine / ws;
+      pw[t * K + myj] = poisoned ? NAN : mine / ws;
     }
   }
   const uint4* xr = reinterpret_cast<const uint4*>(x + t * ldx);

@@ -77,7 +77,9 @@ def route_quant_device(h: torch.Tensor, router_logits: torch.Tensor, top_k: int,
     """Route the T tokens and quantise their hidden rows on the device: -> (xq [T, H] e4m3 bytes,
     xs [T] f32 row scales, offsets [E+1] i32, tok_idx [T*k] i32, tok_w [T*k] f32, inv [T*k] i32),
     the outputs of :func:`topk_softmax` + :func:`route_device` + ``quant_rows`` (bucket order
-    inside an expert may differ; every row is computed independently)."""
+    inside an expert may differ; every row is computed independently).  A row of logits with a NaN,
+    a +inf or nothing but -inf still gets K expert ids in [0, E), each slot stored once, and NaN
+    routing weights (so the token's output row is NaN); the buckets are valid whatever the input."""
     from . import _native as N
     T, H = h.shape
     dev = h.device
@@ -373,11 +375,16 @@ def _fake_quant_mx(x: torch.Tensor) -> torch.Tensor:
     return mx_unblocks((b / sc).to(FP8).float() * sc)
 
 
-def moe_fp8_reference(h, router_w, w13q, s13, w2q, s2, top_k, quant_act=False):
+def moe_fp8_reference(h, router_w, w13q, s13, w2q, s2, top_k, quant_act=False, routing=None):
     """fp32 reference of the fp8 MoE MLP (weights dequantised).  ``quant_act`` additionally rounds
     both GEMM inputs through dynamic per-row fp8, matching the HIP pipeline's arithmetic;
-    ``quant_act="mx"`` rounds the intermediate through MX fp8 (the tiles' MX hand-off) instead."""
-    topw, topi = topk_softmax(h.float() @ router_w.float().t(), top_k)
+    ``quant_act="mx"`` rounds the intermediate through MX fp8 (the tiles' MX hand-off) instead.
+    ``routing`` = (weights [T, k], expert ids [T, k]): use this routing instead of the top-k of
+    ``h @ router_w^T`` (forced routing; a tie rule other than ``torch.topk``'s)."""
+    if routing is None:
+        topw, topi = topk_softmax(h.float() @ router_w.float().t(), top_k)
+    else:
+        topw, topi = routing[0].to(h.device).float(), routing[1].to(h.device).to(torch.int32)
     out = torch.zeros(h.shape, dtype=torch.float32, device=h.device)
     from .activation import silu_mul
     for e in range(w13q.shape[0]):

@@ -154,6 +154,45 @@ def test_mixtral_fp8_prefill_scaled_mm_path():
     assert (got.float() - dec.float()).abs().max().item() < 0.05 * scale
 
 
+def test_mixtral_fp8_mlp_just_above_the_decode_limit_takes_the_tiles(monkeypatch):
+    """One token more than the decode pipeline takes (T = fp8_limit // K + 1): ``MixtralModel.mlp``
+    must run ``moe_prefill_fp8_tiles``, and every token must agree with the same layer on the
+    per-expert hipBLASLt loop (PENNY_MOE_PREFILL_TILES=0).
+
+    Limit per token, ||tiles_t - loop_t|| / ||loop_t|| <= 2^-3: the two paths compute the same
+    sums and differ in how the SiLU intermediate is rounded to e4m3 (MX blocks of 32 against one
+    scale per row), each within 2^-4 of every element, so their intermediates differ by at most
+    2^-3 in norm, and the random W2 carries that ratio to the output row.  A row through a wrong
+    expert or with a term missing is off by 0.5 and more.  Tokens whose bf16 logits tie exactly at
+    the K-th place are left out: ``torch.topk`` (the loop's routing) leaves that choice open."""
+    import numpy as np
+    from financial_chatbot_llm_amd.ops import moe
+    from moe_ref import check_per_token, route_ref
+    cfg = get_model_config("mixtral-tiny")
+    m = MixtralModel(cfg, device="cuda", tp_rank=0, tp_size=1, fp8=True).init_random(seed=5, std=0.05)
+    assert m.prefill_fp8 and "layers.0.w13_q" in m.w
+    K = cfg.top_k_experts
+    T = 1024 // K + 1
+    g = torch.Generator().manual_seed(2)
+    h = torch.randn(T, cfg.hidden_size, generator=g).to(torch.bfloat16).cuda()
+    seen = []
+    real = moe.moe_prefill_fp8_tiles
+    monkeypatch.setattr(moe, "moe_prefill_fp8_tiles", lambda *a, **k: (seen.append(a[0].shape[0]), real(*a, **k))[1])
+    assert moe.PREFILL_TILES
+    got = m.mlp(0, h)
+    assert seen == [T]
+    monkeypatch.setattr(moe, "PREFILL_TILES", False)
+    loop = m.mlp(0, h)
+    assert seen == [T]
+    from financial_chatbot_llm_amd.ops.gemm import linear
+    lg = linear(h, m.w["layers.0.router"]).to(torch.bfloat16).float().cpu().numpy()      # as mlp() forms them
+    srt = -np.sort(-lg, axis=1)
+    tie = srt[:, K - 1] == srt[:, K]
+    assert not route_ref(lg, K).poisoned.any() and tie.mean() < 0.02, tie.sum()
+    ratio = check_per_token(got.cpu()[~tie], loop.cpu()[~tie], 2.0 ** -3, "tiles vs expert loop")
+    print("MOEFIG mixtral-mlp-tiles-vs-loop", f"per_token_max={ratio:.4g} ties={int(tie.sum())}", flush=True)
+
+
 def test_bge_encoder_gpu_matches_cpu():
     from financial_chatbot_llm_amd.models.bert import BertEncoder
     cfg = get_model_config("bert-tiny")
