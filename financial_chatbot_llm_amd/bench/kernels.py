@@ -209,6 +209,99 @@ def bench_prefill(dev) -> List[Dict]:
     return out
 
 
+def _fp8_like(cache: torch.Tensor) -> torch.Tensor:
+    """An fp8 (e4m3) cache with the values of a bf16 one (the element order inside a tile does not matter to
+    a timing run)."""
+    return cache.float().clamp(-448, 448).to(torch.float8_e4m3fn)
+
+
+def bench_kv_fp8_decode(dev) -> List[Dict]:
+    """Lean decode on an fp8 KV cache against the bf16 one: bench_decode_lean's workload batches (B = 64
+    and 128, contexts 1.5-6.5k behind a shared 1k prefix), the engine's launch form (shared blocks
+    marked, lean_flags 3), interleaved rounds in one process."""
+    from ..ops import attention as A
+    out = []
+    g = torch.Generator(device=dev).manual_seed(3)
+    Hq, Hkv, D = 32, 8, 128
+    for B, lo, hi, shared in [(64, 1500, 6500, 1024), (128, 1500, 6500, 1024)]:
+        rng = torch.Generator().manual_seed(B + lo)
+        ctxs = torch.randint(lo, hi, (B,), generator=rng).tolist()
+        nsh = shared // KV_BS
+        W = max((c + KV_BS - 1) // KV_BS for c in ctxs)
+        tables = torch.zeros((B, W), dtype=torch.int32)
+        nxt = nsh
+        for b, c in enumerate(ctxs):
+            nb = (c + KV_BS - 1) // KV_BS
+            tables[b, :nsh] = torch.arange(nsh, dtype=torch.int32)
+            tables[b, nsh:nb] = torch.arange(nxt, nxt + nb - nsh, dtype=torch.int32)
+            nxt += nb - nsh
+        kc = torch.randn((nxt + 1, Hkv, KV_BS * D), generator=g, device=dev).to(torch.bfloat16)
+        vc = torch.randn((nxt + 1, Hkv, KV_BS * D), generator=g, device=dev).to(torch.bfloat16)
+        k8, v8 = _fp8_like(kc), _fp8_like(vc)
+        sc = A.make_kv_scales([0.5] * Hkv, [2.0] * Hkv, dev)
+        q = torch.randn((B, Hq, D), generator=g, device=dev).to(torch.bfloat16)
+        lens = torch.tensor(ctxs, dtype=torch.int32, device=dev)
+        ws = ops.DecodeWorkspace.create(B, Hq, D, 8192, dev)
+        o = torch.empty_like(q)
+        marked = torch.from_numpy(A.mark_shared_blocks(tables.numpy().copy(), np.asarray(ctxs))).to(dev)
+        old = A.LEAN_FLAGS
+        A.LEAN_FLAGS = 3
+        try:
+            ts = interleaved({"bf16": lambda: ops.decode(q, lens, marked, kc, vc, 0.088, workspace=ws, out=o),
+                              "fp8": lambda: ops.decode(q, lens, marked, k8, v8, 0.088, workspace=ws, out=o,
+                                                        kv_scales=sc)}, rounds=9, iters=20)
+        finally:
+            A.LEAN_FLAGS = old
+        elems = (sum(ctxs) - (B - 1) * shared) * Hkv * D * 2          # unique K + V elements
+        row = {"op": "kv_fp8_decode_lean", "B": B, "ctx_range": [lo, hi], "ctx_mean": round(sum(ctxs) / B),
+               "shared": shared, "bf16_us": round(ts["bf16"], 1), "fp8_us": round(ts["fp8"], 1),
+               "speedup": round(ts["bf16"] / ts["fp8"], 3),
+               "bf16_GBps_unique": round(2 * elems / ts["bf16"] / 1e3, 1),
+               "fp8_GBps_unique": round(elems / ts["fp8"] / 1e3, 1)}
+        print(json.dumps(row), flush=True)
+        out.append(row)
+    return out
+
+
+def bench_kv_fp8_prefill(dev) -> List[Dict]:
+    """Prefill attention on an fp8 KV cache (always prefill2 in its variant-5 form) against the default
+    bf16 path (variant 7) and bf16 variant 5, on bench_prefill's shapes and two short-chunk steps the fp8
+    path sends to the big tile (bf16: the 4-wave kernel); interleaved rounds in one process."""
+    out = []
+    g = torch.Generator(device=dev).manual_seed(1)
+    Hq, Hkv, D = 32, 8, 128
+    for S, qlen, ctx in [(16, 512, 1536), (4, 2048, 2048), (1, 8192, 8192), (32, 256, 2048), (16, 9, 5200),
+                         (8, 32, 2048)]:
+        tables, kc, vc, _ = _paged(S, ctx, 0, Hkv, D, dev, g)
+        k8, v8 = _fp8_like(kc), _fp8_like(vc)
+        T = S * qlen
+        q = torch.randn((T, Hq, D), generator=g, device=dev).to(torch.bfloat16)
+        cu = torch.arange(0, T + 1, qlen, dtype=torch.int32, device=dev)
+        lens = torch.full((S,), ctx, dtype=torch.int32, device=dev)
+        o = torch.empty_like(q)
+
+        def bf16(variant):
+            def f():
+                old = ops.attention.prefill_variant(variant)
+                ops.prefill(q, cu, lens, tables, kc, vc, 0.088, True, qlen, out=o)
+                ops.attention.prefill_variant(old)
+            return f
+        ts = interleaved({"bf16_pp7": bf16(7), "bf16_pp5": bf16(5),
+                          "fp8": lambda: ops.prefill(q, cu, lens, tables, k8, v8, 0.088, True, qlen, out=o)},
+                         rounds=7, iters=5)
+        keys = S * (qlen * (ctx - qlen) + qlen * (qlen + 1) / 2)
+        flops = 4 * keys * Hq * D
+        row = {"op": "kv_fp8_prefill_attn", "S": S, "q_len": qlen, "ctx": ctx,
+               "short_chunk": qlen * (Hq // Hkv) <= 128}
+        for k, us in ts.items():
+            row[k + "_us"] = round(us, 1)
+            row[k + "_TFLOPs"] = round(flops / us / 1e6, 1)
+        row["fp8_vs_bf16_default"] = round(ts["bf16_pp7"] / ts["fp8"], 3)
+        print(json.dumps(row), flush=True)
+        out.append(row)
+    return out
+
+
 # prefill-attention launches as the 20-turn RAG workload issues them: (q_len, ctx) per sequence of
 # one mixed step -- respond chunks (~1.6-2k new tokens after a cached system prompt) next to decide
 # prompts (~200 new tokens behind ~4.6k cached ones)
@@ -1683,7 +1776,8 @@ def main(argv=None) -> int:
     dev = torch.device("cuda")
     res = []
     for name in args.only.split(","):
-        res += {"decode": bench_decode, "decode_mixed": bench_decode_mixed, "decode_lean": bench_decode_lean, "prefill": bench_prefill, "prefill_mixed": bench_prefill_mixed, "prefill_spec_split": bench_prefill_spec_split, "elementwise": bench_elementwise,
+        res += {"decode": bench_decode, "decode_mixed": bench_decode_mixed, "decode_lean": bench_decode_lean, "kv_fp8_decode": bench_kv_fp8_decode,
+                "kv_fp8_prefill": bench_kv_fp8_prefill, "prefill": bench_prefill, "prefill_mixed": bench_prefill_mixed, "prefill_spec_split": bench_prefill_spec_split, "elementwise": bench_elementwise,
                 "topk": bench_topk, "gemm": bench_gemm, "gemm_prefill": bench_gemm_prefill, "lm_head": bench_lm_head, "lm_head_fused": bench_lm_head_fused, "lm_head_logprob": bench_lm_head_logprob, "bge_query": bench_bge_query, "gemm_tail": bench_gemm_tail,
                 "gemm_tune": bench_gemm_tune_sweep, "skinny": bench_skinny, "splitk": bench_splitk,
                 "splitk_qkv": lambda d: bench_splitk(d, ("qkv",)), "gateup": bench_gateup, "moe": bench_moe,

@@ -125,6 +125,13 @@ class EngineConfig:
     cp_min_tokens: int = 16384
     cp_layers_per_step: int = 4             # CP prefill layers run per engine step (decode in between)
     kv_block_size: int = 64                 # tokens per KV block (one MFMA KV tile)
+    # KV pool element type: "bf16" | "fp8" (OCP e4m3fn, half the bytes per token: twice the blocks in
+    # the same memory and half the decode-attention HBM traffic; head dim 128, TP = CP = 1).  The
+    # default is read from PENNY_KV_DTYPE when the config is constructed.
+    kv_dtype: str = field(default_factory=lambda: os.getenv("PENNY_KV_DTYPE", "bf16"))
+    # fp8 scales: a safetensors file with k_scale, v_scale [num_layers, num_kv_heads] f32
+    # (engine.kv_calibration.save_kv_scales); None -> 1
+    kv_scales: Optional[str] = None
     # of (free HBM after weights - 6 GiB); 0.92 leaves ~20 GiB of the 288 GiB unused at the end of
     # the 20/5 bench (engine stats hbm_used_gib: 8B 264.5, Mixtral fp8 267.9; 0.95 measured no
     # faster: profiles/r2_bench_kv_fraction.txt)

@@ -30,6 +30,7 @@
 
 #include <cstdlib>
 #include "kv_layout.h"
+#include "kv_fp8.h"
 
 #define LOG2E 1.4426950408889634f
 
@@ -232,7 +233,9 @@ __device__ __forceinline__ void attend_block(const uint4* __restrict__ kl, const
 // logic are the same.  QPRE = true is the prescaled-Q form above: ~32 fewer VALU per block, but
 // bf16(q*c) perturbs each score by ~2^-9 of |s*c|, which shows on very peaky rows (scores of std
 // ~17 log2 units: max error 0.08 vs the fp32 reference where the exact form holds 0.02) -- opt-in.
-template <int D, int MASK, bool SB = false, bool QPRE = false>
+// F8: kl / vl are e4m3 tiles (kv_layout.h): one ds_read_b128 delivers fragments 2p and 2p + 1, converted
+// to bf16 (kv_fp8_to_bf16x8, exact) into the same kfa / vfa registers the MFMAs read.
+template <int D, int MASK, bool SB = false, bool QPRE = false, bool F8 = false>
 __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, const uint4* __restrict__ vl,
                                                   const Frag (&qf)[2][D / 32], f32x4 (&o)[2][D / 16],
                                                   float (&m)[2], f32x4 (&la)[2], bool causal, int j, int ctx,
@@ -241,9 +244,21 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
   constexpr int KC = D / 32;
   constexpr int DT = D / 16;
   Frag kfa[4 * KC], vfa[2 * DT];
+  if constexpr (F8) {
+    uint4 raw[2 * KC];
 #pragma unroll
-  for (int f = 0; f < 4 * KC; ++f) kfa[f].u = kl[f * 64 + lane];
-  if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+    for (int p = 0; p < 2 * KC; ++p) raw[p] = kl[p * 64 + lane];
+    if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < 2 * KC; ++p) {
+      kfa[2 * p].v = kv_fp8_to_bf16x8(raw[p].x, raw[p].y);
+      kfa[2 * p + 1].v = kv_fp8_to_bf16x8(raw[p].z, raw[p].w);
+    }
+  } else {
+#pragma unroll
+    for (int f = 0; f < 4 * KC; ++f) kfa[f].u = kl[f * 64 + lane];
+    if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+  }
   // chains start at -m: the MFMAs deliver s*c - m (m = -inf, a row's first live block: start at 0,
   // and any finite max is a "rise")
   float m0[2], thr[2];
@@ -264,8 +279,14 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
       sc[1][t] = mfma16(kfa[t * KC + c].v, qf[1][c].v, sc[1][t]);
     }
   }
+  uint4 vraw[F8 ? DT : 1];
+  if constexpr (F8) {   // the raw reads fly during the softmax; converted in front of the P.V MFMAs
 #pragma unroll
-  for (int f = 0; f < 2 * DT; ++f) vfa[f].u = vl[f * 64 + lane];
+    for (int p = 0; p < DT; ++p) vraw[p] = vl[p * 64 + lane];
+  } else {
+#pragma unroll
+    for (int f = 0; f < 2 * DT; ++f) vfa[f].u = vl[f * 64 + lane];
+  }
   if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
 
   if (MASK == 1 || (MASK == 2 && need_mask)) {
@@ -331,6 +352,13 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
   // ---- O^T += V^T . P^T, and l += 1 . P^T on the matrix pipe --------------------------------
   Frag ones;
   ones.u = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);   // bf16 1.0 x 8
+  if constexpr (F8) {
+#pragma unroll
+    for (int p = 0; p < DT; ++p) {
+      vfa[2 * p].v = kv_fp8_to_bf16x8(vraw[p].x, vraw[p].y);
+      vfa[2 * p + 1].v = kv_fp8_to_bf16x8(vraw[p].z, vraw[p].w);
+    }
+  }
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
@@ -731,13 +759,22 @@ __device__ __forceinline__ uint4 kv_load(const uint4* p) {
   }
 }
 
-template <int D, bool NT = false>
+// F8: k_cache / v_cache hold e4m3 bytes (kv_layout.h: a lane's 16-B load carries two operand
+// fragments, so a block takes half the loads); fragments are converted to bf16 in registers
+// (kv_fp8_to_bf16x8, exact) in front of the unchanged bf16 MFMAs.  kv_scales [2, Hkv] f32 or null
+// (= 1): K's scale multiplies scale_log2; V's scale is applied exactly once per row segment -- in
+// 1 / l on the direct-output path, on the unnormalised partial O on the split path (the merge
+// kernel is the bf16 one, unchanged).
+template <int D, bool NT = false, bool F8 = false>
 __global__ void __launch_bounds__(256) decode_lean_kernel(
     const bf16* __restrict__ q, const int* __restrict__ ctx_lens, const int* __restrict__ block_tables,
     const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache, bf16* __restrict__ out,
     float* __restrict__ part_m, float* __restrict__ part_l, float* __restrict__ part_o, int* __restrict__ meta,
-    float scale_log2, int B, int Hq, int Hkv, int max_blocks, int nparts, int part_stride, int min_per_wave) {
+    float scale_log2, int B, int Hq, int Hkv, int max_blocks, int nparts, int part_stride, int min_per_wave,
+    const float* __restrict__ kv_scales) {
   constexpr int KC = D / 32, DT = D / 16;
+  constexpr int TILE_B = KV_BS * D * (F8 ? 1 : 2);   // bytes of one (block, kv head) tile
+  static_assert(!F8 || KC % 2 == 0, "fp8 fragment pairs");
   __shared__ int s_pre[LEAN_MAX_B + 1];
   __shared__ int s_w[8];
   const LeanPlan pl = lean_plan(s_pre, s_w, ctx_lens, B, gridDim.x / Hkv * 4, nparts, min_per_wave);
@@ -748,6 +785,13 @@ __global__ void __launch_bounds__(256) decode_lean_kernel(
   const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
   const int h = blockIdx.x % Hkv;
   const int G = Hq / Hkv;
+  float vscale = 1.f;
+  if constexpr (F8) {
+    if (kv_scales != nullptr) {
+      scale_log2 *= kv_scales[h];
+      vscale = kv_scales[Hkv + h];
+    }
+  }
   const int nch = (pl.total + pl.per_wave - 1) / pl.per_wave;
   const int chunk = (blockIdx.x / Hkv) * 4 + (threadIdx.x >> 6);
   if (chunk < nch) {   // no barrier below this point
@@ -790,19 +834,28 @@ __global__ void __launch_bounds__(256) decode_lean_kernel(
       const int id = __builtin_amdgcn_readlane(ids, it & 63);
       const bool shared = id < 0;                          // marked by the host: several rows read it
       const long phys = shared ? -(long)id - 1 : id;
-      const uint4* kb = reinterpret_cast<const uint4*>(k_cache + (phys * Hkv + h) * (long)(KV_BS * D));
-      const uint4* vb = reinterpret_cast<const uint4*>(v_cache + (phys * Hkv + h) * (long)(KV_BS * D));
-      Frag kf[4][KC], vf[DT][2];
+      // tile offset in cache elements: bf16 pointers, so half the element count for 1-byte codes
+      const uint4* kb = reinterpret_cast<const uint4*>(k_cache + (phys * Hkv + h) * (long)(TILE_B / 2));
+      const uint4* vb = reinterpret_cast<const uint4*>(v_cache + (phys * Hkv + h) * (long)(TILE_B / 2));
+      Frag kf[F8 ? 1 : 4][KC], vf[F8 ? 1 : DT][2];
+      uint4 kraw[F8 ? 2 * KC : 1], vraw[F8 ? DT : 1];   // F8: fragments (2p, 2p + 1) per 16-B piece p
       auto load_kv = [&](auto ntc) {
         constexpr bool NTB = decltype(ntc)::value;
+        if constexpr (F8) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+          for (int p = 0; p < 2 * KC; ++p) kraw[p] = kv_load<NTB>(kb + p * 64 + lane);
 #pragma unroll
-          for (int c = 0; c < KC; ++c) kf[t][c].u = kv_load<NTB>(kb + (t * KC + c) * 64 + lane);
+          for (int p = 0; p < DT; ++p) vraw[p] = kv_load<NTB>(vb + p * 64 + lane);
+        } else {
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
+          for (int t = 0; t < 4; ++t)
 #pragma unroll
-          for (int st = 0; st < 2; ++st) vf[dt][st].u = kv_load<NTB>(vb + (dt * 2 + st) * 64 + lane);
+            for (int c = 0; c < KC; ++c) kf[t][c].u = kv_load<NTB>(kb + (t * KC + c) * 64 + lane);
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int st = 0; st < 2; ++st) vf[dt][st].u = kv_load<NTB>(vb + (dt * 2 + st) * 64 + lane);
+        }
       };
       if (NT && !shared) load_kv(std::true_type{});    // wave-uniform branch
       else load_kv(std::false_type{});
@@ -813,7 +866,15 @@ __global__ void __launch_bounds__(256) decode_lean_kernel(
       for (int t = 0; t < 4; ++t) {
         sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < KC; ++c) sc[t] = mfma16(kf[t][c].v, qf[c].v, sc[t]);
+        for (int c = 0; c < KC; ++c) {
+          if constexpr (F8) {   // fragment f = t * KC + c: piece f >> 1, half f & 1 = c & 1
+            const uint4 r = kraw[(t * KC + c) >> 1];
+            const bf16x8 kk = (c & 1) ? kv_fp8_to_bf16x8(r.z, r.w) : kv_fp8_to_bf16x8(r.x, r.y);
+            sc[t] = mfma16(kk, qf[c].v, sc[t]);
+          } else {
+            sc[t] = mfma16(kf[t][c].v, qf[c].v, sc[t]);
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = j * KV_BS + 16 * t + 4 * g + r;
@@ -847,15 +908,20 @@ __global__ void __launch_bounds__(256) decode_lean_kernel(
       l += ls;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        o[dt] = mfma16(vf[dt][0].v, pf[0].v, o[dt]);
-        o[dt] = mfma16(vf[dt][1].v, pf[1].v, o[dt]);
+        if constexpr (F8) {     // fragments 2 dt (keys 0-31) and 2 dt + 1 (keys 32-63): piece dt
+          o[dt] = mfma16(kv_fp8_to_bf16x8(vraw[dt].x, vraw[dt].y), pf[0].v, o[dt]);
+          o[dt] = mfma16(kv_fp8_to_bf16x8(vraw[dt].z, vraw[dt].w), pf[1].v, o[dt]);
+        } else {
+          o[dt] = mfma16(vf[dt][0].v, pf[0].v, o[dt]);
+          o[dt] = mfma16(vf[dt][1].v, pf[1].v, o[dt]);
+        }
       }
     }
     l = rowgroup_sum(l);
     if (col < G) {
       const int hq = h * G + col;
       if (k0 == 0 && k1 == n) {   // whole segment: final output
-        const float inv = 1.f / l;
+        const float inv = F8 ? vscale / l : 1.f / l;
         bf16* orow = out + ((long)b * Hq + hq) * D;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
@@ -868,7 +934,8 @@ __global__ void __launch_bounds__(256) decode_lean_kernel(
         const long pi = ((long)b * Hq + hq) * part_stride + (chunk - seg0 / pl.per_wave);
         PENNY_DASSERT(chunk - seg0 / pl.per_wave < nparts);
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(part_o + pi * D + 16 * dt + 4 * g) = o[dt];
+        for (int dt = 0; dt < DT; ++dt)
+          *reinterpret_cast<f32x4*>(part_o + pi * D + 16 * dt + 4 * g) = F8 ? o[dt] * vscale : o[dt];
         if (g == 0) {
           part_m[pi] = m;
           part_l[pi] = l;
@@ -944,14 +1011,20 @@ struct PrefillLean {
   float* part_ml;       // [slots, Hkv, 256 rows, 2] f32: m (log2 units of the scaled scores), l
 };
 
-template <int D, int NW, int NBUF, bool HEAD_FAST, bool PREF = true, bool SB = false, int FOLD = 0>
-__global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
+// F8 (with FOLD = 1): k_cache / v_cache hold e4m3 bytes -- a tile is KV_BS * D bytes, so PIECES, LOADS
+// and the counted vmcnt waits below halve with it.  kv_scales [2, Hkv] f32 or null (= 1): K's scale
+// folds into scale_log2 (m, the partial m and lse are then in units of the true scores); V's scale
+// into inv / pinv, once on either path (the merge kernel sees partials that already carry it).
+template <int D, int NW, int NBUF, bool HEAD_FAST, bool PREF, bool SB, int FOLD, bool F8>
+__device__ __forceinline__ void prefill2_body(
     const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
     bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
-    float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean = PrefillLean{}) {
+    float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean,
+    const float* __restrict__ kv_scales) {
   constexpr int KC = D / 32, DT = D / 16;
-  constexpr int TILE = KV_BS * D * 2;         // bytes of one K (or V) block tile
+  static_assert(!F8 || FOLD == 1, "the fp8 cache is ported to the FOLD = 1 block loop only");
+  constexpr int TILE = KV_BS * D * (F8 ? 1 : 2);   // bytes of one K (or V) block tile
   constexpr int PIECES = TILE / 1024 / NW;    // 1-KiB glds pieces per wave per tile
   constexpr int LOADS = 2 * PIECES;           // glds per wave per staged block (K + V)
   static_assert(PIECES >= 1 && TILE % (1024 * NW) == 0, "tile must split evenly over the waves");
@@ -986,12 +1059,19 @@ __global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
   const int nblk = li ? min(li[3], nblk_tile) - jb : nblk_tile;
   const int slot = li ? li[4] : -1;
   const int* bt = block_tables + (long)s * max_blocks + jb;
+  float vscale = 1.f;
+  if constexpr (F8) {
+    if (kv_scales != nullptr) {
+      scale_log2 *= kv_scales[h];
+      vscale = kv_scales[Hkv + h];
+    }
+  }
 
   auto stage = [&](int j) {
     const long phys = bt[j];
     PENNY_DASSERT(phys >= 0);
-    const char* kb = reinterpret_cast<const char*>(k_cache + (phys * Hkv + h) * (long)(KV_BS * D));
-    const char* vb = reinterpret_cast<const char*>(v_cache + (phys * Hkv + h) * (long)(KV_BS * D));
+    const char* kb = reinterpret_cast<const char*>(k_cache + (phys * Hkv + h) * (long)(TILE / 2));   // bf16 pointers
+    const char* vb = reinterpret_cast<const char*>(v_cache + (phys * Hkv + h) * (long)(TILE / 2));
     char* kl = smem + (j % NBUF) * 2 * TILE;
     char* vl = kl + TILE;
 #pragma unroll
@@ -1068,8 +1148,8 @@ __global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
     const uint4* vl = reinterpret_cast<const uint4*>(smem + (j % NBUF) * 2 * TILE + TILE);
     const bool full = (ja + 1) * KV_BS <= ctx && (!causal || (ja + 1) * KV_BS - 1 <= ctx - qlen + wave_tok0);
     if constexpr (FOLD != 0)
-      attend_block_fold<D, 2, SB, FOLD == 2>(kl, vl, qf, o, m, la, causal, ja, ctx, qpos, scale_log2, lane, g,
-                                             __builtin_amdgcn_readfirstlane((int)!full) != 0);
+      attend_block_fold<D, 2, SB, FOLD == 2, F8>(kl, vl, qf, o, m, la, causal, ja, ctx, qpos, scale_log2, lane, g,
+                                                 __builtin_amdgcn_readfirstlane((int)!full) != 0);
     else
       attend_block<D, 2, PREF, SB>(kl, vl, qf, o, m, l, causal, ja, ctx, qpos, scale_log2, lane, g,
                                    __builtin_amdgcn_readfirstlane((int)!full) != 0);
@@ -1080,7 +1160,7 @@ __global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
     const float lt = FOLD != 0 ? la[ct][0] : rowgroup_sum(l[ct]);
     if (slot >= 0) {                          // a chunk of a split walk: partial state for the merge
       const long pr = ((long)slot * Hkv + h) * 256 + w * 32 + ct * 16 + col;
-      const float pinv = lt > 0.f ? 1.f / lt : 0.f;
+      const float pinv = lt > 0.f ? (F8 ? vscale / lt : 1.f / lt) : 0.f;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         bf16x4 v4;
@@ -1095,7 +1175,7 @@ __global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
       continue;
     }
     if (tok[ct] >= qlen) continue;
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    const float inv = lt > 0.f ? (F8 ? vscale / lt : 1.f / lt) : 0.f;
     bf16* orow = out + ((long)(q0 + tok[ct]) * Hq + head[ct]) * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -1107,6 +1187,29 @@ __global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
     if (lse != nullptr && g == 0)
       lse[(long)(q0 + tok[ct]) * Hq + head[ct]] = lt > 0.f ? (m[ct] + __log2f(lt)) * 0.6931471805599453f : -INFINITY;
   }
+}
+
+template <int D, int NW, int NBUF, bool HEAD_FAST, bool PREF = true, bool SB = false, int FOLD = 0>
+__global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
+    const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
+    const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
+    bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
+    float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean = PrefillLean{}) {
+  prefill2_body<D, NW, NBUF, HEAD_FAST, PREF, SB, FOLD, false>(q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out,
+                                                               scale_log2, Hq, Hkv, max_blocks, causal, lse, work,
+                                                               lean, nullptr);
+}
+
+// the fp8 (e4m3) cache instantiation: head dim 128, 8 waves, 3 buffers, the FOLD = 1 block loop
+__global__ void __launch_bounds__(512, 1) prefill2_fp8_kernel(
+    const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
+    const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
+    bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
+    float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean,
+    const float* __restrict__ kv_scales) {
+  prefill2_body<128, 8, 3, true, true, true, 1, true>(q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out,
+                                                      scale_log2, Hq, Hkv, max_blocks, causal, lse, work, lean,
+                                                      kv_scales);
 }
 
 // Merge the chunk partials of split tiles (lean prefill): grid (splits, Hkv, 256 / RPB), 256
@@ -1609,12 +1712,12 @@ PENNY_API int penny_attention_decode(const void* q, const int* ctx_lens, const i
       hipLaunchKernelGGL((decode_lean_kernel<DD, true>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q,  \
                          ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m,  \
                          part_l, part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride,            \
-                         lean_min_per_wave);                                                                     \
+                         lean_min_per_wave, (const float*)nullptr);                                              \
     else                                                                                                        \
       hipLaunchKernelGGL((decode_lean_kernel<DD, false>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q, \
                          ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m,  \
                          part_l, part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride,            \
-                         lean_min_per_wave);                                                                     \
+                         lean_min_per_wave, (const float*)nullptr);                                              \
     if (lean_flags & 2)                                                                                         \
       hipLaunchKernelGGL((decode_lean_reduce_kernel<DD, 4>), dim3((Hq + 3) / 4, B), dim3(4 * DD), 0, stream,     \
                          lean_meta, part_m, part_l, part_o, (bf16*)out, B, Hq, part_stride);                      \
@@ -1642,5 +1745,82 @@ PENNY_API int penny_attention_decode(const void* q, const int* ctx_lens, const i
     return (int)hipErrorInvalidValue;
   }
 #undef DECODE_LAUNCH
+  PENNY_RETURN_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------
+// fp8 (e4m3) KV cache entry points: head dim 128, kv_scales [2, Hkv] f32 (K heads, then V heads) or
+// null for 1.  The bf16 entry points above are unchanged.
+// ------------------------------------------------------------------------------------------
+// Lean decode only: the per-(row, head, partition) fallback kernel is not ported.
+PENNY_API int penny_attention_decode_fp8(const void* q, const int* ctx_lens, const int* block_tables,
+                                         const void* k_cache, const void* v_cache, void* out, float* part_m,
+                                         float* part_l, float* part_o, int B, int Hq, int Hkv, int D, int max_blocks,
+                                         int nparts, int part_stride, float scale, int lean_grid, int* lean_meta,
+                                         int lean_min_per_wave, int lean_flags, const float* kv_scales,
+                                         hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (D != 128 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 16 || nparts < 2 || part_stride < nparts || lean_grid <= 0 ||
+      B > LEAN_MAX_B || !lean_meta || lean_min_per_wave < 1 || lean_grid % Hkv || Hkv > LEAN_META0)
+    return (int)hipErrorInvalidValue;
+  const float sl2 = scale * LOG2E;
+  if (lean_flags & 1)
+    hipLaunchKernelGGL((decode_lean_kernel<128, true, true>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q,
+                       ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m, part_l,
+                       part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride, lean_min_per_wave,
+                       kv_scales);
+  else
+    hipLaunchKernelGGL((decode_lean_kernel<128, false, true>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q,
+                       ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m, part_l,
+                       part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride, lean_min_per_wave,
+                       kv_scales);
+  if (lean_flags & 2)
+    hipLaunchKernelGGL((decode_lean_reduce_kernel<128, 4>), dim3((Hq + 3) / 4, B), dim3(4 * 128), 0, stream, lean_meta,
+                       part_m, part_l, part_o, (bf16*)out, B, Hq, part_stride);
+  else
+    hipLaunchKernelGGL((decode_lean_reduce_kernel<128, 1>), dim3(Hq, B), dim3(128), 0, stream, lean_meta, part_m,
+                       part_l, part_o, (bf16*)out, B, Hq, part_stride);
+  PENNY_RETURN_LAUNCH();
+}
+
+// Always prefill2 in its FOLD = 1 form on 256-row tiles, whatever PENNY_PREFILL_PP says and however
+// short the chunks are (the 4-wave short-chunk kernel and prefill3 are not ported); causal only.
+// `work`: prefill_work_list's (sequence, tile) pairs for 256-row tiles, or null for the full grid.
+PENNY_API int penny_attention_prefill_fp8(const void* q, const int* cu_q, const int* ctx_lens,
+                                          const int* block_tables, const void* k_cache, const void* v_cache,
+                                          void* out, int num_seqs, int max_q_len, int Hq, int Hkv, int D,
+                                          int max_blocks, float scale, int causal, float* lse, const int* work,
+                                          int nwork, const float* kv_scales, hipStream_t stream) {
+  if (num_seqs <= 0 || max_q_len <= 0) return 0;
+  if (D != 128 || causal != 1 || Hkv <= 0 || Hq % Hkv || 256 % (Hq / Hkv)) return (int)hipErrorInvalidValue;
+  const int TQ = 256 / (Hq / Hkv);
+  const int ntiles = (max_q_len + TQ - 1) / TQ;
+  const bool wl = work != nullptr && nwork > 0;
+  const dim3 grid = wl ? dim3(Hkv, nwork, 1) : dim3(Hkv, ntiles, num_seqs);
+  hipLaunchKernelGGL(prefill2_fp8_kernel, grid, dim3(512), 0, stream,
+                     (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,
+                     (bf16*)out, scale * LOG2E, Hq, Hkv, max_blocks, 1, lse, wl ? work : (const int*)nullptr,
+                     PrefillLean{}, kv_scales);
+  PENNY_RETURN_LAUNCH();
+}
+
+PENNY_API int penny_attention_prefill_lean_fp8(const void* q, const int* cu_q, const int* ctx_lens,
+                                               const int* block_tables, const void* k_cache, const void* v_cache,
+                                               void* out, int Hq, int Hkv, int D, int max_blocks, float scale,
+                                               int causal, float* lse, const int* items, int nitems,
+                                               const int* merge, int nmerge, void* part_o, float* part_ml,
+                                               const float* kv_scales, hipStream_t stream) {
+  if (nitems <= 0) return 0;
+  if (D != 128 || causal != 1 || Hkv <= 0 || Hq % Hkv || (256 % (Hq / Hkv)) || !items ||
+      (nmerge > 0 && (!merge || !part_o || !part_ml)))
+    return (int)hipErrorInvalidValue;
+  const PrefillLean lean{items, static_cast<bf16*>(part_o), part_ml};
+  hipLaunchKernelGGL(prefill2_fp8_kernel, dim3(Hkv, nitems, 1), dim3(512), 0,
+                     stream, (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache,
+                     (const bf16*)v_cache, (bf16*)out, scale * LOG2E, Hq, Hkv, max_blocks, 1, lse,
+                     (const int*)nullptr, lean, kv_scales);
+  if (nmerge > 0)
+    hipLaunchKernelGGL(prefill_merge_kernel<128>, dim3(nmerge, Hkv, 256 / (4 * (64 / (128 / 4)))), dim3(256), 0, stream,
+                       merge, cu_q, static_cast<const bf16*>(part_o), part_ml, (bf16*)out, lse, Hq, Hkv);
   PENNY_RETURN_LAUNCH();
 }

@@ -13,16 +13,22 @@
 // Rotation is the HF/"neox" rotate-half form used by Llama-3 checkpoints.
 #include "common.h"
 #include "kv_layout.h"
+#include "kv_fp8.h"
 
 // SLAB: the QKV activation arrives as the S f32 split-K slabs [S, T, width] of the QKV GEMM
 // (gemm_splitk.hip) and is reduced here, in the same pass that rotates and scatters it.
 // QK: no paged cache -- rotated q AND k heads go to q_out [T, Hq + Hkv, D] (k heads after the q
 // heads), v is left in qkv: the context-parallel prefill, whose K/V travel the ring as tensors.
-template <int D, bool SLAB, bool QK = false>
-__global__ void rope_kv_kernel(const bf16* __restrict__ qkv, const int* __restrict__ positions,
+// F8: k_cache / v_cache hold e4m3 bytes (kv_layout.h k_index8 / v_index8).  K after RoPE (f32) and V
+// are multiplied by inv_scale [2, Hkv] f32 (K heads, then V heads: 1 / scale, computed once on the
+// host so the reference rounds the same product), clamped to +-448 with NaN kept, and converted
+// round-to-nearest-even.  A K row's 8 consecutive dims are one 8-B store.
+template <int D, bool SLAB, bool QK, bool F8>
+__device__ __forceinline__ void rope_kv_body(const bf16* __restrict__ qkv, const int* __restrict__ positions,
                                const float* __restrict__ cos_sin, const int* __restrict__ slots,
                                bf16* __restrict__ q_out, bf16* __restrict__ k_cache, bf16* __restrict__ v_cache,
-                               int Hq, int Hkv, int apply_rope, const float* __restrict__ P, int S, int T) {
+                               int Hq, int Hkv, int apply_rope, const float* __restrict__ P, int S, int T,
+                               const float* __restrict__ inv_scale) {
   constexpr int HALF = D / 2;
   constexpr int RU = HALF / 8;  // rotary units per head (8 pairs each)
   constexpr int VU = D / 8;     // copy units per v head
@@ -63,6 +69,18 @@ __global__ void rope_kv_kernel(const bf16* __restrict__ qkv, const int* __restri
           x2[i] = b * co[i] + a * si[i];
         }
       }
+      if constexpr (F8) {
+        if (h >= Hq) {
+          if (slot >= 0) {
+            const int kh = h - Hq;
+            const float inv = inv_scale[kh];
+            uint8_t* dst = reinterpret_cast<uint8_t*>(k_cache) + (blk * Hkv + kh) * (long)(KV_BS * D);
+            *reinterpret_cast<uint2*>(dst + k_index8(off, c * 8, D)) = kv_fp8_quant8(x1, inv);
+            *reinterpret_cast<uint2*>(dst + k_index8(off, HALF + c * 8, D)) = kv_fp8_quant8(x2, inv);
+          }
+          continue;
+        }
+      }
       const uint4 p1 = pack8(x1), p2 = pack8(x2);
       if (QK) {
         bf16* dst = q_out + ((long)t * (Hq + Hkv) + h) * D;
@@ -83,11 +101,38 @@ __global__ void rope_kv_kernel(const bf16* __restrict__ qkv, const int* __restri
       const int h = v / VU, c = v % VU;
       float x[8];
       load8((Hq + Hkv + h) * D + c * 8, x);
+      if constexpr (F8) {
+        const uint2 pk = kv_fp8_quant8(x, inv_scale[Hkv + h]);
+        uint8_t* base8 = reinterpret_cast<uint8_t*>(v_cache) + (blk * Hkv + h) * (long)(KV_BS * D);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          base8[v_index8(off, c * 8 + i, D)] = (uint8_t)((i < 4 ? pk.x : pk.y) >> (8 * (i & 3)));
+        continue;
+      }
       bf16* base = v_cache + (blk * Hkv + h) * (long)(KV_BS * D);
 #pragma unroll
       for (int i = 0; i < 8; ++i) base[v_index(off, c * 8 + i, D)] = (bf16)x[i];
     }
   }
+}
+
+template <int D, bool SLAB, bool QK = false>
+__global__ void rope_kv_kernel(const bf16* __restrict__ qkv, const int* __restrict__ positions,
+                               const float* __restrict__ cos_sin, const int* __restrict__ slots,
+                               bf16* __restrict__ q_out, bf16* __restrict__ k_cache, bf16* __restrict__ v_cache,
+                               int Hq, int Hkv, int apply_rope, const float* __restrict__ P, int S, int T) {
+  rope_kv_body<D, SLAB, QK, false>(qkv, positions, cos_sin, slots, q_out, k_cache, v_cache, Hq, Hkv, apply_rope, P, S,
+                                   T, nullptr);
+}
+
+template <bool SLAB>
+__global__ void rope_kv_fp8_kernel(const bf16* __restrict__ qkv, const int* __restrict__ positions,
+                                   const float* __restrict__ cos_sin, const int* __restrict__ slots,
+                                   bf16* __restrict__ q_out, bf16* __restrict__ k_cache, bf16* __restrict__ v_cache,
+                                   int Hq, int Hkv, int apply_rope, const float* __restrict__ P, int S, int T,
+                                   const float* __restrict__ inv_scale) {
+  rope_kv_body<128, SLAB, false, true>(qkv, positions, cos_sin, slots, q_out, k_cache, v_cache, Hq, Hkv, apply_rope,
+                                       P, S, T, inv_scale);
 }
 
 template <bool SLAB>
@@ -107,6 +152,36 @@ static int launch_rope_kv(const void* qkv, const float* P, int S, const int* pos
     return (int)hipErrorInvalidValue;
   }
   PENNY_RETURN_LAUNCH();
+}
+
+// fp8 (e4m3) caches, head dim 128: inv_scale [2, Hkv] f32 (see rope_kv_kernel F8)
+template <bool SLAB>
+static int launch_rope_kv_fp8(const void* qkv, const float* P, int S, const int* positions, const float* cos_sin,
+                              const int* slots, void* q_out, void* k_cache, void* v_cache, const float* inv_scale,
+                              int T, int Hq, int Hkv, int D, int apply_rope, hipStream_t stream) {
+  if (T <= 0) return 0;
+  if (D != 128 || !inv_scale) return (int)hipErrorInvalidValue;
+  const dim3 grid(T, T <= 512 ? 2 : 1);
+  hipLaunchKernelGGL(rope_kv_fp8_kernel<SLAB>, grid, dim3(256), 0, stream, (const bf16*)qkv, positions,
+                     cos_sin, slots, (bf16*)q_out, (bf16*)k_cache, (bf16*)v_cache, Hq, Hkv, apply_rope, P, S, T,
+                     inv_scale);
+  PENNY_RETURN_LAUNCH();
+}
+
+PENNY_API int penny_rope_kv_write_fp8(const void* qkv, const int* positions, const float* cos_sin, const int* slots,
+                                      void* q_out, void* k_cache, void* v_cache, const float* inv_scale, int T,
+                                      int Hq, int Hkv, int D, int apply_rope, hipStream_t stream) {
+  return launch_rope_kv_fp8<false>(qkv, nullptr, 0, positions, cos_sin, slots, q_out, k_cache, v_cache, inv_scale, T,
+                                   Hq, Hkv, D, apply_rope, stream);
+}
+
+PENNY_API int penny_rope_kv_write_slabs_fp8(const void* P, int S, const int* positions, const float* cos_sin,
+                                            const int* slots, void* q_out, void* k_cache, void* v_cache,
+                                            const float* inv_scale, int T, int Hq, int Hkv, int D, int apply_rope,
+                                            hipStream_t stream) {
+  if (S < 1) return (int)hipErrorInvalidValue;
+  return launch_rope_kv_fp8<true>(nullptr, (const float*)P, S, positions, cos_sin, slots, q_out, k_cache, v_cache,
+                                  inv_scale, T, Hq, Hkv, D, apply_rope, stream);
 }
 
 PENNY_API int penny_rope_kv_write(const void* qkv, const int* positions, const float* cos_sin, const int* slots,

@@ -53,10 +53,42 @@ class ScoreResult:
     top1_match: List[bool]
 
 
+def kv_elt_bytes(cfg: EngineConfig) -> int:
+    return 1 if getattr(cfg, "kv_dtype", "bf16") == "fp8" else 2
+
+
+def check_kv_dtype(cfg: EngineConfig, model) -> None:
+    """The fp8 KV cache's limits, refused up front with a clear error."""
+    kd = getattr(cfg, "kv_dtype", "bf16")
+    if kd not in ("bf16", "fp8"):
+        raise ValueError(f"unknown kv_dtype {kd!r} (bf16 | fp8)")
+    if kd != "fp8":
+        return
+    if cfg.tp_size > 1 or getattr(model, "tp_size", 1) > 1 or getattr(cfg, "cp_size", 1) > 1 \
+            or getattr(cfg, "shard_of_tp", 0):
+        raise NotImplementedError("fp8 KV cache: tensor / context parallel engines (tp_size, cp_size, "
+                                  "shard_of_tp) are not supported yet")
+    if model.D != 128:
+        raise ValueError(f"fp8 KV cache needs head dim 128, got {model.D}")
+
+
+def load_kv_scales(path: Optional[str], num_layers: int, num_kv_heads: int):
+    """(k_scale, v_scale) [L, Hkv] f32 from a ``kv_scales`` safetensors file, or (None, None)."""
+    if not path:
+        return None, None
+    from safetensors import safe_open
+    with safe_open(path, framework="pt") as fh:
+        ks, vs = fh.get_tensor("k_scale").float(), fh.get_tensor("v_scale").float()
+    for t in (ks, vs):
+        if tuple(t.shape) != (num_layers, num_kv_heads):
+            raise ValueError(f"{path}: kv scales must be [{num_layers}, {num_kv_heads}], got {tuple(t.shape)}")
+    return ks, vs
+
+
 def plan_kv_blocks(cfg: EngineConfig, model, device) -> int:
     if cfg.num_kv_blocks:
         return cfg.num_kv_blocks
-    per_block = KVCache.bytes_per_block(model.cfg.num_layers, model.hkv, model.D)
+    per_block = KVCache.bytes_per_block(model.cfg.num_layers, model.hkv, model.D, elt=kv_elt_bytes(cfg))
     if device.type != "cuda":
         return max(64, (cfg.max_num_seqs * cfg.max_model_len // KV_BS) // 8)
     free, _ = torch.cuda.mem_get_info(device)
@@ -79,9 +111,14 @@ class LLMEngine:
             self.gemm_tuning = load_gemm_tuning(cfg.model, cfg.tp_size)
         self.tokenizer = tokenizer or load_tokenizer(cfg.tokenizer, self.model.cfg.vocab_size)
         self.eos_ids = set(self.tokenizer.eos_ids)
+        check_kv_dtype(cfg, self.model)
         nblocks = plan_kv_blocks(cfg, self.model, device)
+        kv_dtype = getattr(cfg, "kv_dtype", "bf16")
+        ks, vs = (load_kv_scales(getattr(cfg, "kv_scales", None), self.model.cfg.num_layers, self.model.hkv)
+                  if kv_dtype == "fp8" else (None, None))
         self.kv = KVCache(self.model.cfg.num_layers, nblocks, self.model.hkv, self.model.D,
-                          dtype=getattr(self.model, "dtype", torch.bfloat16), device=device)
+                          dtype=getattr(self.model, "dtype", torch.bfloat16), device=device, kv_dtype=kv_dtype,
+                          k_scale=ks, v_scale=vs)
         self.bm = make_block_manager(nblocks, KV_BS, cfg.enable_prefix_caching)
         base, per_row, per_tok = cfg.step_cost_ms
         self.scheduler = Scheduler(self.bm, cfg.max_num_seqs, cfg.max_num_batched_tokens, cfg.max_model_len,
@@ -707,6 +744,7 @@ class LLMEngine:
                 "scored_tokens": self.scored_tokens,
                 "constrained_tokens": self.runner.stats["constrained_tokens"],
                 "constrained_steps": self.runner.stats["constrained_steps"],
+                "kv_dtype": self.kv.kv_dtype,
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),
                 "preemptions": self.scheduler.num_preemptions,
@@ -749,4 +787,4 @@ class LLMEngine:
         return {"hbm_used_gib": round((total - free) / g, 1), "hbm_total_gib": round(total / g, 1),
                 "torch_peak_reserved_gib": round(torch.cuda.max_memory_reserved(self.device) / g, 1),
                 "kv_pool_gib": round(self.bm.num_blocks * KVCache.bytes_per_block(
-                    self.model.cfg.num_layers, self.model.hkv, self.model.D) / g, 1)}
+                    self.model.cfg.num_layers, self.model.hkv, self.model.D, elt=self.kv.elt) / g, 1)}

@@ -236,7 +236,8 @@ class DecoderModel:
         T = h.shape[0]
         kc, vc = kv.k(i), kv.v(i)
         scale, qpre = self.scale, False
-        if qkv_rope_fused(h, self.w[p + "qkv"], self.D):
+        kvs = kv.scales(i)                        # fp8 cache: this layer's per-head scales (else None)
+        if qkv_rope_fused(h, self.w[p + "qkv"], self.D, kc):
             # prefill step: QKV GEMM with RoPE + paged KV write in its epilogue (K3+K4+K5, one pass).
             # PRESCALE_Q: q leaves it times scale * log2(e) at its one bf16 rounding, so the prefill
             # attention's block loop needs no per-score multiply (the prescaled-Q fold) without the
@@ -251,7 +252,8 @@ class DecoderModel:
             # QKV is column-parallel: even under TP its split-K slabs go straight to the RoPE/KV-write
             # pass (no all-reduce in between), unlike the row-parallel O / down projections
             qkv = linear(h, self.w[p + "qkv"], wt=self.wt.get(p + "qkv"), slabs=True)
-            q = ops.rope_kv_write(qkv, positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv, self.D)
+            q = ops.rope_kv_write(qkv, positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv, self.D,
+                                  kv_scales=kvs)
         attn = torch.empty_like(q)
         tp = meta.num_prefill_tokens
         side = None
@@ -267,17 +269,17 @@ class DecoderModel:
             ev_fork.record(main)
             side.wait_event(ev_fork)
             ops.decode(q[tp:], meta.ctx_lens_d, meta.block_tables_d, kc, vc, scale,
-                       workspace=meta.decode_ws, out=attn[tp:], stream=side.cuda_stream)
+                       workspace=meta.decode_ws, out=attn[tp:], stream=side.cuda_stream, kv_scales=kvs)
         if tp > 0:
             ops.prefill(q[:tp], meta.cu_q, meta.ctx_lens_p, meta.block_tables_p, kc, vc, scale,
                         causal=meta.causal, max_q_len=meta.max_q_len, out=attn[:tp], work=meta.prefill_work,
-                        lean=meta.prefill_lean, q_prescaled=qpre)
+                        lean=meta.prefill_lean, q_prescaled=qpre, kv_scales=kvs)
         if side is not None:
             ev_join.record(side)
             main.wait_event(ev_join)
         elif meta.num_decode > 0:
             ops.decode(q[tp:], meta.ctx_lens_d, meta.block_tables_d, kc, vc, scale,
-                       workspace=meta.decode_ws, out=attn[tp:])
+                       workspace=meta.decode_ws, out=attn[tp:], kv_scales=kvs)
         out = linear(attn.view(T, self.hq * self.D), self.w[p + "o"], wt=self.wt.get(p + "o"),
                      slabs=self.tp_size == 1, fuse_residual=fuse_residual)
         return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out

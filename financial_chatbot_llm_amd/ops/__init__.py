@@ -5,8 +5,8 @@ loudly if the library is missing), CPU tensors run an fp32 PyTorch reference tha
 oracle in the numerics tests.
 """
 from .activation import gelu_, silu_mul
-from .attention import (KV_BS, DecodeWorkspace, decode, default_scale, prefill, rope_cos_sin, rope_kv_write,
-                        write_kv_ref)
+from .attention import (KV_BS, DecodeWorkspace, KVScales, decode, default_scale, gather_kv_ref, kv_dequant,
+                        make_kv_scales, prefill, rope_cos_sin, rope_kv_write, write_kv_ref)
 from .embedding import embedding
 from .norm import layer_norm, rms_norm
 from .retrieval import filtered_topk
@@ -16,5 +16,5 @@ from .sampling import (apply_top_k_top_p, fused_lm_head_ok, fused_logprob_ok, lm
 from .constrain import FsmTables, build_masks, sample_constrained
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
-           "rope_kv_write", "write_kv_ref", "embedding", "layer_norm", "rms_norm", "filtered_topk",
+           "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",
            "apply_top_k_top_p", "sample"]

@@ -6,6 +6,10 @@ of ``64*D`` elements per (block, kv head), stored in MFMA-fragment-native order:
     k_cache[layer]: [num_blocks, Hkv, 64*D]   element (key, d) at K_INDEX[D][key, d]
     v_cache[layer]: [num_blocks, Hkv, 64*D]   element (key, d) at V_INDEX[D][key, d]
 
+With an fp8 (OCP e4m3fn) cache the tiles are ``64*D`` bytes at ``k_index8`` / ``v_index8`` (two
+consecutive fragments share a lane's 16 bytes) and every op here dispatches on the cache dtype;
+``kv_scales`` (:class:`KVScales`, per kv head, default 1) maps codes to values: ``value = code * scale``.
+
 The torch reference implementations here are the numerics oracle for the HIP kernels (fp32
 math on the same bf16 inputs) and the CPU path used by the CI tests.
 """
@@ -16,7 +20,7 @@ import math
 import os
 from dataclasses import dataclass
 from functools import lru_cache
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -36,6 +40,99 @@ def v_index(key: int, d: int, D: int) -> int:
     dt, row, s, k = d >> 4, d & 15, key >> 5, key & 31
     g, j = (k & 15) >> 2, ((k >> 4) << 2) + (k & 3)
     return (((dt * 2 + s) * 64 + g * 16 + row) << 3) + j
+
+
+def k_index8(key: int, d: int, D: int) -> int:
+    """Byte index of K element (key, d) in an fp8 tile: fragment f = t*(D/32) + c of the bf16 layout,
+    fragments 2p and 2p + 1 in bytes 0-7 and 8-15 of lane piece p."""
+    t, r, c, g, j = key >> 4, key & 15, d >> 5, (d >> 3) & 3, d & 7
+    f = t * (D >> 5) + c
+    return (((f >> 1) * 64 + g * 16 + r) << 4) + ((f & 1) << 3) + j
+
+
+def v_index8(key: int, d: int, D: int) -> int:
+    dt, row, s, k = d >> 4, d & 15, key >> 5, key & 31
+    g, j = (k & 15) >> 2, ((k >> 4) << 2) + (k & 3)
+    f = dt * 2 + s
+    return (((f >> 1) * 64 + g * 16 + row) << 4) + ((f & 1) << 3) + j
+
+
+@lru_cache(maxsize=None)
+def kv_index_tables8(D: int):
+    """(K_INDEX8, V_INDEX8) [64, D] long tensors: byte positions in an fp8 tile."""
+    ki = torch.tensor([[k_index8(k, d, D) for d in range(D)] for k in range(KV_BS)], dtype=torch.long)
+    vi = torch.tensor([[v_index8(k, d, D) for d in range(D)] for k in range(KV_BS)], dtype=torch.long)
+    return ki, vi
+
+
+# --------------------------------------------------------------------------------------------
+# fp8 (e4m3fn) cache: scales and the reference quantiser
+# --------------------------------------------------------------------------------------------
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def is_fp8(cache: torch.Tensor) -> bool:
+    return cache.dtype == FP8
+
+
+class KVScales(NamedTuple):
+    """Per-kv-head scales of one layer's fp8 cache, ``value = code * scale``: ``scale`` and ``inv``
+    are f32 [2, Hkv] (row 0: K, row 1: V).  ``inv = 1 / scale`` is computed ONCE on the host
+    (:func:`make_kv_scales`) and the writer kernel and the reference multiply by that same tensor,
+    so both round the same product."""
+    scale: torch.Tensor
+    inv: torch.Tensor
+
+
+def make_kv_scales(k_scale, v_scale, device="cpu") -> KVScales:
+    sc = torch.stack([torch.as_tensor(k_scale, dtype=torch.float32).cpu().reshape(-1),
+                      torch.as_tensor(v_scale, dtype=torch.float32).cpu().reshape(-1)])
+    if not bool((sc > 0).all()) or not bool(torch.isfinite(sc).all()):
+        raise ValueError("kv scales must be positive and finite")
+    return KVScales(sc.to(device), (1.0 / sc).to(device))
+
+
+_UNIT_SCALES: Dict[tuple, KVScales] = {}
+
+
+def _unit_scales(Hkv: int, device) -> KVScales:
+    key = (Hkv, str(device))
+    if key not in _UNIT_SCALES:
+        one = torch.ones((2, Hkv), dtype=torch.float32, device=device)
+        _UNIT_SCALES[key] = KVScales(one, one)
+    return _UNIT_SCALES[key]
+
+
+def quantize_kv_ref(x: torch.Tensor, inv_scale: Optional[torch.Tensor]) -> torch.Tensor:
+    """Reference quantiser: x [T, Hkv, D] -> e4m3 codes of ``x * inv_scale[h]`` (f32 product, clamp to
+    +-448 with NaN kept -- torch's own cast turns overflow into NaN -- round to nearest even)."""
+    y = x.float()
+    if inv_scale is not None:
+        y = y * inv_scale.float().to(y.device)[None, :, None]
+    return y.clamp(-FP8_MAX, FP8_MAX).to(FP8)          # clamp propagates NaN
+
+
+def kv_dequant(cache_fp8: torch.Tensor, scales: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp8 tiles [..., Hkv, 64*D] (K or V alike) -> the same tiles as bf16 in the bf16 layout;
+    ``scales`` [Hkv] f32 multiplies each head's values before the bf16 rounding.  HIP
+    (``penny_kv_dequant_fp8``, the attention kernels' own conversion helper) on the GPU."""
+    assert is_fp8(cache_fp8) and cache_fp8.dim() >= 2
+    Hkv, n = cache_fp8.shape[-2], cache_fp8.shape[-1]
+    D = n // KV_BS
+    if D != 128:
+        raise ValueError(f"fp8 KV cache needs head dim 128, got {D}")
+    src = cache_fp8.contiguous()
+    out = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
+    if N.use_native(src):
+        sc = scales.to(torch.float32).contiguous() if scales is not None else None
+        N.call("penny_kv_dequant_fp8", N.ptr(src), N.ptr(out), N.ptr(sc), src.numel() // n, Hkv, D, N.stream())
+        return out
+    f = src.float().view(-1, n // 16, 2, 8)             # [tile, piece, fragment parity, element]
+    f = f.view(-1, n // 1024, 64, 2, 8).permute(0, 1, 3, 2, 4).reshape(src.shape)   # piece (p, lane) -> fragment 2p + parity
+    if scales is not None:
+        f = f * scales.float().to(f.device)[:, None]
+    return f.to(torch.bfloat16)
 
 
 @lru_cache(maxsize=None)
@@ -73,28 +170,41 @@ def rope_cos_sin(D: int, max_pos: int, theta: float, scaling: Optional[dict] = N
 
 
 def _rope_ref(x: torch.Tensor, pos: torch.Tensor, cos_sin: torch.Tensor) -> torch.Tensor:
+    return _rope_f32(x, pos, cos_sin).to(x.dtype)
+
+
+def _rope_f32(x: torch.Tensor, pos: torch.Tensor, cos_sin: torch.Tensor) -> torch.Tensor:
     D = x.shape[-1]
     cs = cos_sin[pos.long()]
     cos, sin = cs[:, None, : D // 2], cs[:, None, D // 2:]
     xf = x.float()
     x1, x2 = xf[..., : D // 2], xf[..., D // 2:]
-    return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1).to(x.dtype)
+    return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
 
 
 # --------------------------------------------------------------------------------------------
 # KV write
 # --------------------------------------------------------------------------------------------
 def write_kv_ref(k: torch.Tensor, v: torch.Tensor, slots: torch.Tensor, k_cache: torch.Tensor,
-                 v_cache: torch.Tensor) -> None:
-    """k, v [T, Hkv, D] -> paged fragment-native caches (skips slots < 0)."""
+                 v_cache: torch.Tensor, kv_scales: Optional[KVScales] = None) -> None:
+    """k, v [T, Hkv, D] -> paged fragment-native caches (skips slots < 0).  An fp8 cache is
+    quantised on write (:func:`quantize_kv_ref`)."""
     sl = slots.long()
     keep = sl >= 0
     if not bool(keep.any()):
         return
     sl, k, v = sl[keep], k[keep], v[keep]
     D = k.shape[-1]
-    ki, vi = kv_index_tables(D)
     blk, off = sl // KV_BS, sl % KV_BS
+    if is_fp8(k_cache):
+        ki, vi = kv_index_tables8(D)
+        kq = quantize_kv_ref(k, kv_scales.inv[0] if kv_scales is not None else None).view(torch.uint8)
+        vq = quantize_kv_ref(v, kv_scales.inv[1] if kv_scales is not None else None).view(torch.uint8)
+        kc, vc = k_cache.view(torch.uint8).permute(0, 2, 1), v_cache.view(torch.uint8).permute(0, 2, 1)
+        kc[blk[:, None], ki.to(sl.device)[off]] = kq.transpose(1, 2)
+        vc[blk[:, None], vi.to(sl.device)[off]] = vq.transpose(1, 2)
+        return
+    ki, vi = kv_index_tables(D)
     kc, vc = k_cache.permute(0, 2, 1), v_cache.permute(0, 2, 1)   # [NB, 64*D, Hkv] views
     kc[blk[:, None], ki.to(sl.device)[off]] = k.transpose(1, 2).to(k_cache.dtype)
     vc[blk[:, None], vi.to(sl.device)[off]] = v.transpose(1, 2).to(v_cache.dtype)
@@ -102,13 +212,24 @@ def write_kv_ref(k: torch.Tensor, v: torch.Tensor, slots: torch.Tensor, k_cache:
 
 def rope_kv_write(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional[torch.Tensor],
                   slots: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, Hq: int, Hkv: int,
-                  D: int, apply_rope: bool = True) -> torch.Tensor:
+                  D: int, apply_rope: bool = True, kv_scales: Optional[KVScales] = None) -> torch.Tensor:
     """Rotate q/k of a fused QKV activation, write k/v into the paged cache, return q [T,Hq,D].
-    ``qkv`` may be the unreduced :class:`~.gemm.Slabs` of the split-K QKV GEMM (summed here)."""
+    ``qkv`` may be the unreduced :class:`~.gemm.Slabs` of the split-K QKV GEMM (summed here).
+    fp8 cache: K after RoPE (f32, no bf16 rounding in between) and V are quantised with
+    ``kv_scales.inv`` (``penny_rope_kv_write_fp8`` / ``_slabs_fp8``)."""
+    fp8 = is_fp8(k_cache)
+    if fp8 and D != 128:
+        raise ValueError(f"fp8 KV cache needs head dim 128, got {D}")
     if isinstance(qkv, Slabs):
         S, T, _ = qkv.P.shape
         if N.use_native(qkv.P):
             q = torch.empty((T, Hq, D), dtype=torch.bfloat16, device=qkv.P.device)
+            if fp8:
+                inv = (kv_scales or _unit_scales(Hkv, q.device)).inv
+                N.call("penny_rope_kv_write_slabs_fp8", N.ptr(qkv.P), S, N.ptr(positions),
+                       N.ptr(cos_sin) if apply_rope else None, N.ptr(slots), N.ptr(q), N.ptr(k_cache),
+                       N.ptr(v_cache), N.ptr(inv), T, Hq, Hkv, D, int(apply_rope), N.stream())
+                return q
             N.call("penny_rope_kv_write_slabs", N.ptr(qkv.P), S, N.ptr(positions),
                    N.ptr(cos_sin) if apply_rope else None, N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache),
                    T, Hq, Hkv, D, int(apply_rope), N.stream())
@@ -117,14 +238,21 @@ def rope_kv_write(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional[
     T = qkv.shape[0]
     if N.use_native(qkv):
         q = torch.empty((T, Hq, D), dtype=qkv.dtype, device=qkv.device)
+        if fp8:
+            inv = (kv_scales or _unit_scales(Hkv, q.device)).inv
+            N.call("penny_rope_kv_write_fp8", N.ptr(qkv), N.ptr(positions), N.ptr(cos_sin) if apply_rope else None,
+                   N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache), N.ptr(inv), T, Hq, Hkv, D,
+                   int(apply_rope), N.stream())
+            return q
         N.call("penny_rope_kv_write", N.ptr(qkv), N.ptr(positions), N.ptr(cos_sin) if apply_rope else None,
                N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache), T, Hq, Hkv, D, int(apply_rope), N.stream())
         return q
     x = qkv.view(T, Hq + 2 * Hkv, D)
     q, k, v = x[:, :Hq], x[:, Hq:Hq + Hkv], x[:, Hq + Hkv:]
     if apply_rope:
-        q, k = _rope_ref(q, positions, cos_sin), _rope_ref(k, positions, cos_sin)
-    write_kv_ref(k, v, slots, k_cache, v_cache)
+        # fp8: the rotated K goes to the quantiser in f32, as in the kernel
+        q, k = _rope_ref(q, positions, cos_sin), (_rope_f32 if fp8 else _rope_ref)(k, positions, cos_sin)
+    write_kv_ref(k, v, slots, k_cache, v_cache, kv_scales)
     return q.contiguous()
 
 
@@ -147,17 +275,27 @@ def rope_qk(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, H
     return _rope_ref(qkv.view(T, -1, D)[:, :Hq + Hkv], positions, cos_sin).to(qkv.dtype)
 
 
-def gather_kv_ref(k_cache: torch.Tensor, v_cache: torch.Tensor, blocks: torch.Tensor, n: int):
-    """-> K, V [n, Hkv, D] for one sequence (inverse of the paged layout)."""
+def gather_kv_ref(k_cache: torch.Tensor, v_cache: torch.Tensor, blocks: torch.Tensor, n: int,
+                  kv_scales: Optional[KVScales] = None):
+    """-> K, V [n, Hkv, D] for one sequence (inverse of the paged layout).  An fp8 cache is
+    upcast: f32 ``code * scale``."""
     Hkv = k_cache.shape[1]
     D = k_cache.shape[2] // KV_BS
-    ki, vi = kv_index_tables(D)
+    fp8 = is_fp8(k_cache)
+    ki, vi = kv_index_tables8(D) if fp8 else kv_index_tables(D)
     nb = (n + KV_BS - 1) // KV_BS
     b = blocks[:nb].long()
+    if fp8:
+        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
     kt = k_cache[b][..., ki.to(b.device).flatten()].view(nb, Hkv, KV_BS, D)
     vt = v_cache[b][..., vi.to(b.device).flatten()].view(nb, Hkv, KV_BS, D)
     k = kt.permute(0, 2, 1, 3).reshape(nb * KV_BS, Hkv, D)
     v = vt.permute(0, 2, 1, 3).reshape(nb * KV_BS, Hkv, D)
+    if fp8:
+        k, v = k.contiguous().view(FP8).float(), v.contiguous().view(FP8).float()
+        if kv_scales is not None:
+            k = k * kv_scales.scale[0].float().to(k.device)[None, :, None]
+            v = v * kv_scales.scale[1].float().to(v.device)[None, :, None]
     return k[:n], v[:n]
 
 
@@ -352,7 +490,8 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
             k_cache: torch.Tensor, v_cache: torch.Tensor, scale: float, causal: bool = True,
             max_q_len: Optional[int] = None, out: Optional[torch.Tensor] = None,
             lse: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None,
-            lean: Optional[Tuple[int, int, int]] = None, q_prescaled: bool = False) -> torch.Tensor:
+            lean: Optional[Tuple[int, int, int]] = None, q_prescaled: bool = False,
+            kv_scales: Optional[KVScales] = None) -> torch.Tensor:
     """Varlen paged attention for the new tokens of S sequences (chunked prefill / prefix hits:
     query i of sequence s sits at absolute position ctx_lens[s] - q_len[s] + i).  ``lse`` [T, Hq]
     f32 (optional) receives each row's natural-log sum-exp of the scaled scores (-inf: no key
@@ -360,8 +499,18 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
     step on the device (optional; LPT tile order), or :func:`prefill_lean_list`'s split-KV list
     (``lean`` = its (items, merges, slots) counts, read from the header when not given).
     ``q_prescaled``: q already carries ``scale * log2(e)`` (``prefill_qkv_rope(qscale=...)``) and
-    ``scale`` is ``1 / log2(e)``; the big tiles then run the prescaled-Q fold."""
+    ``scale`` is ``1 / log2(e)``; the big tiles then run the prescaled-Q fold.
+    fp8 cache (causal, head dim 128, q not prescaled): always the 8-wave ``prefill2`` kernel in its
+    variant-5 form on 256-row tiles -- ``PENNY_PREFILL_PP`` is ignored and short chunks take it too."""
     T, Hq, D = q.shape
+    fp8 = is_fp8(k_cache)
+    if fp8:
+        if not causal:
+            raise ValueError("fp8 KV cache: non-causal prefill attention is not supported")
+        if q_prescaled:
+            raise ValueError("fp8 KV cache: prescaled q is not supported")
+        if D != 128:
+            raise ValueError(f"fp8 KV cache needs head dim 128, got {D}")
     flags = int(causal) | (2 if q_prescaled else 0)
     Hkv = k_cache.shape[1]
     S = block_tables.shape[0]
@@ -372,6 +521,13 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
             # lean work list (prefill_lean_list): the counts ride along host-side as ``lean``
             ni, nm, nslots = lean if lean is not None else (int(work[0, 1]), int(work[0, 2]), int(work[0, 3]))
             po, pml = _lean_workspace(q.device, max(nslots, 1), Hkv, D)
+            if fp8:
+                N.call("penny_attention_prefill_lean_fp8", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens),
+                       N.ptr(block_tables), N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), Hq, Hkv, D,
+                       block_tables.shape[1], float(scale), flags, N.ptr(lse) if lse is not None else None,
+                       N.ptr(work[1:]), int(ni), N.ptr(work[1 + ni:]) if nm else None, int(nm), N.ptr(po), N.ptr(pml),
+                       N.ptr(kv_scales.scale) if kv_scales is not None else None, N.stream())
+                return out
             N.call("penny_attention_prefill_lean", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens), N.ptr(block_tables),
                    N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), Hq, Hkv, D, block_tables.shape[1], float(scale),
                    flags, N.ptr(lse) if lse is not None else None, N.ptr(work[1:]), int(ni),
@@ -379,6 +535,13 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
             return out
         if max_q_len is None:
             max_q_len = int((cu_q[1:] - cu_q[:-1]).max().item())
+        if fp8:
+            N.call("penny_attention_prefill_fp8", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens), N.ptr(block_tables),
+                   N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), S, int(max_q_len), Hq, Hkv, D, block_tables.shape[1],
+                   float(scale), flags, N.ptr(lse) if lse is not None else None,
+                   N.ptr(work) if work is not None else None, int(work.shape[0]) if work is not None else 0,
+                   N.ptr(kv_scales.scale) if kv_scales is not None else None, N.stream())
+            return out
         N.call("penny_attention_prefill", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens), N.ptr(block_tables),
                N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), S, int(max_q_len), Hq, Hkv, D, block_tables.shape[1],
                float(scale), flags, N.ptr(lse) if lse is not None else None,
@@ -391,7 +554,7 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
         a, b = cu[s], cu[s + 1]
         if b <= a:
             continue
-        k, v = gather_kv_ref(k_cache, v_cache, block_tables[s], ctx[s])
+        k, v = gather_kv_ref(k_cache, v_cache, block_tables[s], ctx[s], kv_scales)
         out[a:b] = _attend_ref(q[a:b], k, v, scale, ctx[s] - (b - a) if causal else None).to(q.dtype)
         if lse is not None:
             lse[a:b] = _lse_ref(q[a:b], k, scale, ctx[s] - (b - a) if causal else None)
@@ -545,12 +708,17 @@ def fork_join_events(device) -> Tuple["torch.cuda.Event", "torch.cuda.Event"]:
 def decode(q: torch.Tensor, ctx_lens: torch.Tensor, block_tables: torch.Tensor, k_cache: torch.Tensor,
            v_cache: torch.Tensor, scale: float, workspace: Optional[DecodeWorkspace] = None,
            max_ctx: Optional[int] = None, out: Optional[torch.Tensor] = None,
-           stream: Optional[int] = None) -> torch.Tensor:
+           stream: Optional[int] = None, kv_scales: Optional[KVScales] = None) -> torch.Tensor:
     """One query token per sequence against its paged context: the work-balanced split-K kernel
     (``decode_lean_kernel``) by default, the per-(row, head, partition) kernel with
-    ``PENNY_DECODE_LEAN=0``.  ``stream``: raw HIP stream to launch on (default: the current one)."""
+    ``PENNY_DECODE_LEAN=0``.  ``stream``: raw HIP stream to launch on (default: the current one).
+    fp8 cache: the lean kernel only (the fallback kernel is not ported: an error where the lean
+    path is unavailable)."""
     B, Hq, D = q.shape
     Hkv = k_cache.shape[1]
+    fp8 = is_fp8(k_cache)
+    if fp8 and D != 128:
+        raise ValueError(f"fp8 KV cache needs head dim 128, got {D}")
     if N.use_native(q):
         out = torch.empty_like(q) if out is None else out
         if workspace is None or workspace.part_m.shape[0] < B or workspace.part_m.shape[1] < Hq:
@@ -560,6 +728,17 @@ def decode(q: torch.Tensor, ctx_lens: torch.Tensor, block_tables: torch.Tensor, 
         ws = workspace
         lean = (DECODE_LEAN and B >= LEAN_MIN_B and ws.lean_meta is not None
                 and ws.lean_meta.numel() >= LEAN_META0 + B + 2)
+        if fp8:
+            if not lean:
+                raise RuntimeError("fp8 KV cache: decode attention needs the lean kernel (PENNY_DECODE_LEAN=1, "
+                                   "PENNY_DECODE_LEAN_MIN_B <= batch, and a workspace with lean_meta)")
+            N.call("penny_attention_decode_fp8", N.ptr(q), N.ptr(ctx_lens), N.ptr(block_tables), N.ptr(k_cache),
+                   N.ptr(v_cache), N.ptr(out), N.ptr(ws.part_m), N.ptr(ws.part_l), N.ptr(ws.part_o), B, Hq, Hkv, D,
+                   block_tables.shape[1], ws.nparts, ws.part_stride, float(scale), _lean_grid(q.device, Hkv),
+                   N.ptr(ws.lean_meta), LEAN_MIN_PER_WAVE, LEAN_FLAGS if B >= LEAN_NT_MIN_B else LEAN_FLAGS & ~1,
+                   N.ptr(kv_scales.scale) if kv_scales is not None else None,
+                   N.stream() if stream is None else stream)
+            return out
         pb, nparts = ws.partitioning(B) if not lean else (ws.pb, ws.nparts)
         args = [N.ptr(q), N.ptr(ctx_lens), N.ptr(block_tables), N.ptr(k_cache), N.ptr(v_cache), N.ptr(out),
                 N.ptr(ws.part_m), N.ptr(ws.part_l), N.ptr(ws.part_o), B, Hq, Hkv, D, block_tables.shape[1], pb,
@@ -572,7 +751,7 @@ def decode(q: torch.Tensor, ctx_lens: torch.Tensor, block_tables: torch.Tensor, 
     ctx = ctx_lens.tolist()
     block_tables = torch.where(block_tables < 0, -block_tables - 1, block_tables)   # shared-block marks
     for b in range(B):
-        k, v = gather_kv_ref(k_cache, v_cache, block_tables[b], ctx[b])
+        k, v = gather_kv_ref(k_cache, v_cache, block_tables[b], ctx[b], kv_scales)
         out[b:b + 1] = _attend_ref(q[b:b + 1], k, v, scale, None).to(q.dtype)
     return out
 

@@ -646,8 +646,11 @@ def mid_linear(x: torch.Tensor, w: torch.Tensor, S: int, epilogue: Optional[str]
     return splitk_reduce(P, residual=residual)
 
 
-def qkv_rope_fused(x: torch.Tensor, w: torch.Tensor, D: int) -> bool:
-    """Does this prefill step run the fused QKV + RoPE + KV-write tile kernel?"""
+def qkv_rope_fused(x: torch.Tensor, w: torch.Tensor, D: int, k_cache: Optional[torch.Tensor] = None) -> bool:
+    """Does this prefill step run the fused QKV + RoPE + KV-write tile kernel?  Never for an fp8
+    ``k_cache``: the fused epilogue writes bf16 tiles only."""
+    if k_cache is not None and k_cache.dtype == torch.float8_e4m3fn:
+        return False
     M, K = x.shape
     N_ = w.shape[0]
     if D != 128 or M <= 256 or not prefill_ok(x, w):

@@ -112,6 +112,8 @@ def create_app(services: Services, start_consumer: bool = True) -> FastAPI:
         if services.engine is not None and hasattr(services.engine, "stats"):
             for k, v in services.engine.stats().items():
                 for kk, vv in (v.items() if isinstance(v, dict) else ((None, v),)):
+                    if isinstance(vv, str):       # labels such as kv_dtype are not gauges
+                        continue
                     METRICS.set_gauge(f"engine_{k}" if kk is None else f"engine_{k}_{kk}", float(vv))
         return METRICS.render_prometheus()
 

@@ -48,6 +48,10 @@ def parse(argv=None):
                     default=os.environ.get("PENNY_CONSTRAIN_TOOLCALLS", "0").lower() in ("1", "true", "yes"),
                     help="decide calls sample under the tool-call token automaton (TP = 1 only)")
     ap.add_argument("--max-model-len", type=int, default=8192)
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default=os.environ.get("PENNY_KV_DTYPE", "bf16"),
+                    help="KV pool element type (fp8: e4m3, twice the tokens in the same memory; TP = CP = 1)")
+    ap.add_argument("--kv-scales", default=os.environ.get("PENNY_KV_SCALES") or None,
+                    help="fp8 KV scales file (safetensors: k_scale, v_scale [layers, kv heads])")
     ap.add_argument("--device", default=None)
     ap.add_argument("--no-http", action="store_true")
     ap.add_argument("--smoke", action="store_true", help="serve one synthetic turn from the in-memory broker and exit")
@@ -125,6 +129,7 @@ def main(argv=None) -> int:
     cp_follower = ps.cp_size > 1 and ps.cp_rank != 0
     ecfg = config.EngineConfig.from_env(model=args.model, tp_size=args.tp, max_model_len=args.max_model_len,
                                         device=dev_type, use_cuda_graph=dev_type == "cuda", cp_size=args.cp,
+                                        kv_dtype=args.kv_dtype, kv_scales=args.kv_scales,
                                         # a CP follower never decodes: a token KV pool, no graphs
                                         **({"num_kv_blocks": 16} if cp_follower else {}))
     engine = LLMEngine(ecfg)

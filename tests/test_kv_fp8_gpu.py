@@ -1,0 +1,365 @@
+"""fp8 (e4m3) paged KV cache on the GPU: the conversion helper over all 256 codes, the writer against
+the reference quantiser, lean decode and big-tile prefill against the CPU path ON THE SAME fp8 CACHE
+(every e4m3 value is exact in bf16, so the error budget is the bf16 kernels' own: the attention
+tolerance of tests/test_kernels_gpu.py), the model and the engine.  Hkv = 2, D = 128, G = 4 and 8.
+"""
+import numpy as np
+import pytest
+import torch
+
+import kv_fp8_ref as R
+from financial_chatbot_llm_amd import ops
+from financial_chatbot_llm_amd.config import EngineConfig
+from financial_chatbot_llm_amd.engine import LLMEngine, SamplingParams
+from financial_chatbot_llm_amd.models.configs import get_model_config
+from financial_chatbot_llm_amd.models.llama import LlamaModel
+from financial_chatbot_llm_amd.models.mixtral import MixtralModel
+from financial_chatbot_llm_amd.ops import attention as A
+from financial_chatbot_llm_amd.ops.gemm import Slabs
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+D, HKV, KV_BS = R.D, R.HKV, R.KV_BS
+SCALE = 1 / D ** 0.5
+HQS = [8, 16]
+SETTINGS = [R.UNIT, R.SCALED]
+IDS = ["unit", "scaled"]
+
+
+def close(a, b, atol=2e-2, rtol=0.02):
+    """tests/test_kernels_gpu.py ``close`` (the project's attention tolerance)."""
+    a, b = a.float().cpu(), b.float().cpu()
+    err = (a - b).abs()
+    tol = atol + rtol * b.abs()
+    assert bool((err <= tol).all()), f"max err {err.max().item():.4g} (atol {atol})"
+
+
+def rnd(*shape, gen=None):
+    return torch.randn(*shape, generator=gen).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------
+# conversion helper
+# ---------------------------------------------------------------------------------------------
+def test_code_table_exact():
+    """kv_dequant (the attention kernels' conversion helper) over all 256 byte codes == torch's cast."""
+    c = torch.arange(256, dtype=torch.uint8).repeat(HKV * KV_BS * D // 256).view(1, HKV, KV_BS * D)
+    fp8 = c.view(A.FP8)
+    got = ops.kv_dequant(fp8.to(DEV)).float().cpu()
+    want = A.kv_dequant(fp8).float()                       # CPU path: torch's .float() of the codes, re-laid
+    assert torch.equal(torch.isnan(got), torch.isnan(want)) and int(torch.isnan(want).sum()) == 2 * want.numel() // 256
+    assert torch.equal(torch.nan_to_num(got, nan=0.0), torch.nan_to_num(want, nan=0.0))
+    # every code value appears, and the bf16 layout agrees with the fp8 one through the gather
+    bt = torch.tensor([0])
+    k8, v8 = A.gather_kv_ref(fp8, fp8, bt, KV_BS)
+    k16, v16 = A.gather_kv_ref(got.to(torch.bfloat16), got.to(torch.bfloat16), bt, KV_BS)
+    assert torch.equal(torch.nan_to_num(k8), torch.nan_to_num(k16.float()))
+    assert torch.equal(torch.nan_to_num(v8), torch.nan_to_num(v16.float()))
+    sc = torch.tensor([0.5, 3.0])
+    gs = ops.kv_dequant(fp8.to(DEV), sc.to(DEV)).float().cpu()
+    assert torch.equal(torch.nan_to_num(gs), torch.nan_to_num(A.kv_dequant(fp8, sc).float()))
+
+
+# ---------------------------------------------------------------------------------------------
+# writer
+# ---------------------------------------------------------------------------------------------
+def _writer_inputs(Hq, gen):
+    T = 75
+    W = (Hq + 2 * HKV) * D
+    # multiples of 2^-6: the f32 slabs below then sum exactly in any order, and x * inv_scale lands on
+    # many round-to-nearest-even ties and in the subnormal range
+    qkv = torch.round(torch.randn(T, W, generator=gen) * 2.0 * 64) / 64 + 0.0     # + 0.0: no -0 (a slab sum gives +0)
+    qkv[3, Hq * D + 17] = 1000.0                 # K head 0: saturates
+    qkv[9, (Hq + HKV) * D + 5] = 1000.0          # V head 0
+    qkv[11, (Hq + 1) * D + 40] = float("nan")    # K head 1
+    qkv[20, (Hq + HKV + 1) * D + 99] = float("nan")
+    qkv = qkv.to(torch.bfloat16)
+    slots = torch.arange(60, 60 + T, dtype=torch.int32)
+    slots[7] = -1
+    pos = torch.randint(0, 4000, (T,), generator=gen, dtype=torch.int32)
+    return qkv, slots, pos
+
+
+def _slabs_of(qkv, gen, S=4):
+    """S f32 slabs whose sum is exactly ``qkv`` (bf16, multiples of 2^-6): the first carries qkv minus the
+    multiples of 2^-4 in the others."""
+    x = qkv.float()
+    noise = [torch.round(torch.randn(x.shape, generator=gen) * 4) / 16 for _ in range(S - 1)]
+    first = x - sum(noise)
+    P = torch.stack([first] + noise)
+    P = torch.where(torch.isnan(x)[None], torch.stack([x] + [torch.zeros_like(x)] * (S - 1)), P)
+    return P.contiguous()
+
+
+@pytest.mark.parametrize("Hq", HQS)
+@pytest.mark.parametrize("slab", [False, True], ids=["bf16", "slabs"])
+def test_writer(Hq, slab):
+    g = torch.Generator().manual_seed(11)
+    qkv, slots, pos = _writer_inputs(Hq, g)
+    sc = R.scales(R.SCALED)
+    scd = R.scales(R.SCALED, DEV)
+    cs = ops.rope_cos_sin(D, 4096, 500000.0)
+    src = qkv
+    if slab:
+        P = _slabs_of(qkv, g)
+        assert torch.equal(torch.nan_to_num(P.sum(0).to(torch.bfloat16).float()), torch.nan_to_num(qkv.float()))
+        src = Slabs(P.to(DEV))
+    for apply_rope in (False, True):
+        kc, vc = R.empty_cache(3), R.empty_cache(3)
+        kd, vd = R.empty_cache(3, DEV), R.empty_cache(3, DEV)
+        qr = ops.rope_kv_write(qkv, pos, cs, slots, kc, vc, Hq, HKV, D, apply_rope, kv_scales=sc)
+        q = ops.rope_kv_write(src if slab else qkv.to(DEV), pos.to(DEV), cs.to(DEV), slots.to(DEV), kd, vd, Hq, HKV,
+                              D, apply_rope, kv_scales=scd)
+        close(q, qr)
+        for name, got, want in (("v", R.codes(vd), R.codes(vc)), ("k", R.codes(kd), R.codes(kc))):
+            nan_w, nan_g = R.is_nan_code(want), R.is_nan_code(got)
+            assert torch.equal(nan_w, nan_g), f"{name}: NaN codes moved"     # a NaN stays a NaN code
+            # the rotation pairs dims d and d + 64: a NaN in one makes both NaN
+            assert int(nan_w.sum()) == (2 if name == "k" and apply_rope else 1)
+            got, want = got[~nan_w].int(), want[~nan_w].int()
+            if name == "v" or not apply_rope:
+                assert torch.equal(got, want), f"{name} rope={apply_rope}: {(got != want).sum()} codes differ"
+            else:
+                # f32 FMA order of the rotation differs: equal or adjacent codes (sign-magnitude bytes are
+                # monotone within a sign; +-0 count as adjacent to the smallest subnormals), <= 1 in 1000
+                diff = got != want
+                mag = ((got & 0x7F) - (want & 0x7F)).abs()
+                same_sign = (got & 0x80) == (want & 0x80)
+                adjacent = (same_sign & (mag <= 1)) | (~same_sign & ((got & 0x7F) + (want & 0x7F) <= 1))
+                assert bool(adjacent.all()), "a K code is more than one step from the reference"
+                written = int((want != 0).sum())
+                print(f"writer rope G={Hq // HKV} slab={slab}: {int(diff.sum())} of {written} K codes differ")
+                assert int(diff.sum()) * 1000 <= written
+        if not apply_rope:       # 1000 saturated to 448 (code 0x7E), not NaN: head 0 scales are 0.5 (K), 2.0 (V)
+            assert int((R.codes(vd) == 0x7E).sum()) >= 1 and int((R.codes(kd) == 0x7E).sum()) >= 1
+
+
+# ---------------------------------------------------------------------------------------------
+# decode
+# ---------------------------------------------------------------------------------------------
+CTXS = (1, 63, 64, 65, 777, 2500)
+
+
+@pytest.fixture(scope="module")
+def decode_case():
+    out = {}
+    for si, setting in enumerate(SETTINGS):
+        g = torch.Generator().manual_seed(21 + si)
+        sc = R.scales(setting)
+        tables, nb = R.tables_for(CTXS, g)
+        tables[4, :2] = tables[5, :2]                       # rows 4 and 5 share their first two blocks
+        kc, vc = R.random_cache(nb, sc, g)
+        out[si] = (sc, tables, kc, vc, kc.to(DEV), vc.to(DEV))
+    return out
+
+
+@pytest.mark.parametrize("Hq", HQS)
+@pytest.mark.parametrize("si", [0, 1], ids=IDS)
+@pytest.mark.parametrize("flags", [0, 3])
+def test_decode(decode_case, Hq, si, flags, monkeypatch):
+    sc, tables, kc, vc, kcd, vcd = decode_case[si]
+    scd = R.scales(SETTINGS[si], DEV)
+    g = torch.Generator().manual_seed(5)
+    B = len(CTXS)
+    q = rnd(B, Hq, D, gen=g)
+    ctx = torch.tensor(CTXS, dtype=torch.int32)
+    ref = ops.decode(q, ctx, tables, kc, vc, SCALE, kv_scales=sc)
+    monkeypatch.setattr(A, "LEAN_FLAGS", flags)
+    monkeypatch.setattr(A, "LEAN_NT_MIN_B", 1)             # bit 0 (non-temporal loads) at this batch size too
+    ws = ops.DecodeWorkspace.create(B, Hq, D, max(CTXS), DEV)
+    marked = tables.clone()
+    marked[4:6, :2] = -marked[4:6, :2] - 1                 # the engine's shared-block marks
+    outs = []
+    for bt in (tables, marked):
+        o = ops.decode(q.to(DEV), ctx.to(DEV), bt.to(DEV), kcd, vcd, SCALE, workspace=ws, kv_scales=scd)
+        close(o, ref)
+        outs.append(o)
+    assert torch.equal(outs[0], outs[1])                   # the marks change the cache policy only
+    # not gated: distance to the bf16 kernel on the dequantised cache
+    kb = ops.kv_dequant(kcd, scd.scale[0] if scd else None)
+    vb = ops.kv_dequant(vcd, scd.scale[1] if scd else None)
+    ob = ops.decode(q.to(DEV), ctx.to(DEV), tables.to(DEV), kb, vb, SCALE, workspace=ws)
+    print(f"decode G={Hq // HKV} {IDS[si]} flags={flags}: max |fp8 - bf16 kernel| = "
+          f"{(outs[0].float() - ob.float()).abs().max().item():.3g}, max |fp8 - ref| = "
+          f"{(outs[0].float().cpu() - ref.float()).abs().max().item():.3g}")
+
+
+def test_decode_needs_lean_workspace(decode_case):
+    sc, tables, kc, vc, kcd, vcd = decode_case[0]
+    B, Hq = len(CTXS), 8
+    ws = ops.DecodeWorkspace.create(B, Hq, D, max(CTXS), DEV)
+    ws.lean_meta = None
+    with pytest.raises(RuntimeError, match="lean"):
+        ops.decode(rnd(B, Hq, D).to(DEV), torch.tensor(CTXS, dtype=torch.int32).to(DEV), tables.to(DEV), kcd, vcd,
+                   SCALE, workspace=ws)
+
+
+# ---------------------------------------------------------------------------------------------
+# prefill
+# ---------------------------------------------------------------------------------------------
+PREFILL_CASES = {                       # name: (q lens, ctx lens)
+    "q300": ([300], [300]),
+    "q70_behind_500": ([70], [570]),
+    "q5_behind_70": ([5], [75]),
+    "two_seqs": ([130, 33], [130, 400]),
+    "lean_2_behind_1500": ([2], [1502]),
+}
+
+
+@pytest.fixture(scope="module")
+def prefill_cache():
+    out = {}
+    for si, setting in enumerate(SETTINGS):
+        g = torch.Generator().manual_seed(31 + si)
+        sc = R.scales(setting)
+        nb = 40
+        kc, vc = R.random_cache(nb, sc, g)
+        out[si] = (sc, nb, kc, vc, kc.to(DEV), vc.to(DEV))
+    return out
+
+
+@pytest.mark.parametrize("Hq", HQS)
+@pytest.mark.parametrize("si", [0, 1], ids=IDS)
+@pytest.mark.parametrize("case", list(PREFILL_CASES))
+def test_prefill(prefill_cache, Hq, si, case):
+    sc, nb, kc, vc, kcd, vcd = prefill_cache[si]
+    scd = R.scales(SETTINGS[si], DEV)
+    qlens, ctxs = PREFILL_CASES[case]
+    g = torch.Generator().manual_seed(7)
+    need = [(c + KV_BS - 1) // KV_BS for c in ctxs]
+    assert sum(need) <= nb
+    perm = torch.randperm(nb, generator=g)
+    tables = torch.zeros((len(ctxs), max(need)), dtype=torch.int32)
+    k = 0
+    for i, n in enumerate(need):
+        tables[i, :n] = perm[k:k + n].to(torch.int32)
+        k += n
+    T = sum(qlens)
+    q = rnd(T, Hq, D, gen=g)
+    cu = torch.tensor([0] + list(np.cumsum(qlens)), dtype=torch.int32)
+    ctx = torch.tensor(ctxs, dtype=torch.int32)
+    lse_ref = torch.empty(T, Hq)
+    ref = ops.prefill(q, cu, ctx, tables, kc, vc, SCALE, True, lse=lse_ref, kv_scales=sc)
+    kw = {}
+    if case.startswith("lean"):
+        wl = A.prefill_lean_list(cu.numpy(), ctx.numpy(), Hq // HKV, HKV, True, cus=100000, min_chunk=4)
+        assert wl is not None and int(wl[0, 2]) > 0 and int(wl[0, 3]) > 1      # merge slots are used
+        kw = dict(work=torch.from_numpy(wl).to(DEV), lean=(int(wl[0, 1]), int(wl[0, 2]), int(wl[0, 3])))
+    lse = torch.full((T, Hq), float("nan"), device=DEV)
+    out = ops.prefill(q.to(DEV), cu.to(DEV), ctx.to(DEV), tables.to(DEV), kcd, vcd, SCALE, True, max_q_len=max(qlens),
+                      lse=lse, kv_scales=scd, **kw)
+    print(f"prefill {case} G={Hq // HKV} {IDS[si]}: max |out - ref| = "
+          f"{(out.float().cpu() - ref.float()).abs().max().item():.3g}, max |lse - ref| = "
+          f"{(lse.cpu() - lse_ref).abs().max().item():.3g}")
+    close(out, ref)
+    close(lse, lse_ref)
+    if case == "two_seqs":           # the step's LPT work list (256-row tiles) gives the same rows
+        wl2 = A.prefill_work_list(cu.numpy(), ctx.numpy(), Hq // HKV, True)
+        assert wl2 is not None
+        out2 = ops.prefill(q.to(DEV), cu.to(DEV), ctx.to(DEV), tables.to(DEV), kcd, vcd, SCALE, True,
+                           max_q_len=max(qlens), work=torch.from_numpy(wl2).to(DEV), kv_scales=scd)
+        assert torch.equal(out2, out)
+
+
+def test_prefill_non_causal_errors(prefill_cache):
+    sc, nb, kc, vc, kcd, vcd = prefill_cache[0]
+    q = rnd(5, 8, D).to(DEV)
+    cu = torch.tensor([0, 5], dtype=torch.int32, device=DEV)
+    ctx = torch.tensor([5], dtype=torch.int32, device=DEV)
+    bt = torch.zeros((1, 1), dtype=torch.int32, device=DEV)
+    with pytest.raises(ValueError, match="causal"):
+        ops.prefill(q, cu, ctx, bt, kcd, vcd, SCALE, causal=False, max_q_len=5)
+    # the launcher refuses it too
+    from financial_chatbot_llm_amd.ops import _native as N
+    out = torch.empty_like(q)
+    rc = N.load().penny_attention_prefill_fp8(N.ptr(q), N.ptr(cu), N.ptr(ctx), N.ptr(bt), N.ptr(kcd), N.ptr(vcd),
+                                              N.ptr(out), 1, 5, 8, HKV, D, 1, SCALE, 0, None, None, 0, None, N.stream())
+    assert rc != 0
+
+
+@pytest.mark.parametrize("Hq", HQS)
+@pytest.mark.parametrize("si", [0, 1], ids=IDS)
+def test_decode_matches_prefill_last_row(prefill_cache, Hq, si):
+    sc, nb, kc, vc, kcd, vcd = prefill_cache[si]
+    scd = R.scales(SETTINGS[si], DEV)
+    g = torch.Generator().manual_seed(6)
+    L = 517
+    tables = torch.randperm(nb, generator=g)[:(L + KV_BS - 1) // KV_BS].to(torch.int32)[None]
+    q = rnd(L, Hq, D, gen=g)
+    cu = torch.tensor([0, L], dtype=torch.int32)
+    ctx = torch.tensor([L], dtype=torch.int32)
+    a = ops.prefill(q.to(DEV), cu.to(DEV), ctx.to(DEV), tables.to(DEV), kcd, vcd, SCALE, True, L, kv_scales=scd)
+    b = ops.decode(q[-1:].to(DEV), ctx.to(DEV), tables.to(DEV), kcd, vcd, SCALE, kv_scales=scd)
+    close(a[-1:], b)
+
+
+# ---------------------------------------------------------------------------------------------
+# model
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["llama-tiny", "mixtral-tiny"])
+def test_model_forward_fp8_kv(name):
+    cfg = get_model_config(name)
+    cls = MixtralModel if cfg.arch == "mixtral" else LlamaModel
+    gpu = cls(cfg, device="cuda", tp_rank=0, tp_size=1).init_random(seed=1)
+    cpu = cls(cfg, device="cpu", tp_rank=0, tp_size=1)
+    cpu.w = {k: v.cpu() for k, v in gpu.w.items()}
+    ids = list(range(3, 3 + 200))
+    b16 = R.logits(cpu, ids, "bf16")
+    b = R.logits(cpu, ids, "fp8")
+    a = R.logits(gpu, ids, "fp8")
+    e_q = (b - b16).abs().mean().item()                    # what quantising the cache costs, reference alone
+    base = 0.01 * b.abs().max().item() + 0.01              # the bf16 bound of test_gpu_forward_matches_cpu_reference
+    err = (a - b).abs().mean().item()
+    print(f"{name}: mean |GPU fp8 - CPU fp8| = {err:.4g}; bound = {base:.4g} (bf16 term) + {e_q:.4g} (e_q)")
+    assert err <= base + e_q, (err, base, e_q)
+
+
+# ---------------------------------------------------------------------------------------------
+# engine
+# ---------------------------------------------------------------------------------------------
+BASE = dict(model="llama-tiny", device="cuda", num_kv_blocks=160, max_model_len=2048, max_num_seqs=16,
+            max_num_batched_tokens=512, graph_batch_sizes=(1, 2, 4, 8, 16), seed=0)
+
+
+def test_engine_fp8_kv():
+    long = list(range(1000, 2500))                        # 1500 tokens: three 512-token chunks
+    short = [list(range(100 + 7 * i, 100 + 7 * i + 30 + 17 * i)) for i in range(8)]
+    sp = SamplingParams(temperature=0.0, max_tokens=40, ignore_eos=True)
+    e1 = LLMEngine(EngineConfig(use_cuda_graph=False, kv_dtype="fp8", **BASE))
+    assert e1.kv.buf.dtype == torch.float8_e4m3fn and e1.stats()["kv_dtype"] == "fp8"
+    eager = e1.generate([long] + short, sp)
+    assert all(len(o) == 40 for o in eager)
+    assert e1.runner.stats["prefill_steps"] >= 3
+    e2 = LLMEngine(EngineConfig(use_cuda_graph=True, kv_dtype="fp8", **BASE), model=e1.model)
+    e2.warmup()
+    graph = e2.generate([long] + short, sp)
+    assert e2.runner.stats["graph_steps"] >= 30
+    agree = sum(a == b for x, y in zip(eager, graph) for a, b in zip(x, y)) / (9 * 40)
+    assert agree >= 0.9, (eager, graph)
+    # a prefix-cache hit gives the greedy tokens of a cold run (eager both)
+    sp8 = SamplingParams(temperature=0.0, max_tokens=8, ignore_eos=True)
+    h0 = e1.bm.hit_rate()
+    again = e1.generate([long[:1300] + [7, 8, 9]], sp8)[0]
+    assert e1.bm.hit_rate() > h0
+    cold = LLMEngine(EngineConfig(use_cuda_graph=False, kv_dtype="fp8", enable_prefix_caching=False, **BASE),
+                     model=e1.model)
+    assert again == cold.generate([long[:1300] + [7, 8, 9]], sp8)[0]
+    # score(): runs; distance to the bf16-KV engine is reported, not gated
+    ref = LLMEngine(EngineConfig(use_cuda_graph=False, **BASE), model=e1.model)
+    assert ref.kv.buf.dtype == torch.bfloat16
+    s8 = torch.tensor(e2.score(long[:700]).logprobs)
+    s16 = torch.tensor(ref.score(long[:700]).logprobs)
+    assert s8.shape == (699,) and bool(torch.isfinite(s8).all())
+    print(f"score(): mean |fp8-KV - bf16-KV| = {(s8 - s16).abs().mean().item():.4g} nats over 699 tokens")
+    # prompt-lookup speculation and a constrained request complete
+    rep = list(range(300, 340)) * 4
+    out = e2.generate([rep], SamplingParams(temperature=0.0, max_tokens=24, ignore_eos=True, prompt_lookup=4))[0]
+    assert len(out) == 24
+    from financial_chatbot_llm_amd.agent.automaton import compile_tool_automaton
+    from test_constrain_cpu import PROBE
+    auto = compile_tool_automaton([PROBE], e2.tokenizer)
+    seq = e2.add_request("c0", list(range(300, 340)),
+                         SamplingParams(temperature=1.0, max_tokens=96, seed=1000, constraint=auto))
+    while not seq.finished or e2.has_work():
+        e2.step()
+    assert seq.finish_reason == "stop" and e2.stats()["constrained_steps"] > 0
