@@ -7,6 +7,7 @@ prefix (8-rank shapes: test_world8_gpu.py).
 the column-parallel QKV shard's f32 slabs feed the RoPE/KV-write pass under TP (the path Llama-3-70B
 TP=8 takes) while the row-parallel O / down outputs are all-reduced.
 """
+import io
 import os
 import socket
 
@@ -76,7 +77,11 @@ def _worker(rank, world, port, q, graphs=False):
             assert comm._CUSTOM_AR is not None and int(comm._CUSTOM_AR.counter.item()) > 0
             comm._CUSTOM_AR.check()
         torch.cuda.synchronize()
-        q.put((rank, (out, logits.cpu())))
+        # by value: a tensor would travel as a file descriptor that the parent has to fetch from this
+        # process, which may have exited by then (EOFError in the parent)
+        buf = io.BytesIO()
+        torch.save(logits.cpu(), buf)
+        q.put((rank, (out, buf.getvalue())))
         shutdown()
     except Exception:  # noqa: BLE001
         import traceback
@@ -102,6 +107,7 @@ def test_tp2_gpu_matches_tp1(monkeypatch, graphs):
     for r, v in res.items():
         assert not (isinstance(v, str) and v.startswith("ERR")), v
     got, logits2 = res[0]
+    logits2 = torch.load(io.BytesIO(logits2))
     from test_world8_gpu import _assert_logits_close
     # numbers, not tokens: the TP=2 prefill logits match TP=1 within bf16 noise (a shard bug that
     # corrupts a few heads moves them far beyond it), and every TP=2 greedy token is, within the
