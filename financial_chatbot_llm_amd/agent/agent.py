@@ -59,8 +59,13 @@ class LLMAgent:
                  max_decide_tokens: int = 160, max_tool_steps: int = 1,
                  today_fn: Callable[[], _dt.date] = _dt.date.today,
                  system_prompt: Optional[str] = None, tool_prompt: Optional[str] = None,
-                 max_transaction_tokens: Optional[int] = config.MAX_TRANSACTION_TOKENS):
+                 max_transaction_tokens: Optional[int] = config.MAX_TRANSACTION_TOKENS,
+                 decide_logprobs: bool = False, decide_confidence_threshold: float = 0.5):
         self.llm = llm
+        # decide confidence (ServingConfig.decide_logprobs): the decide call asks for the sampled
+        # tokens' log-probabilities and exp(mean) goes to the metrics registry
+        self.decide_logprobs = bool(decide_logprobs)
+        self.decide_confidence_threshold = float(decide_confidence_threshold)
         self.retrieval_tool = retrieval_tool
         self.tools: Dict[str, Tool] = {retrieval_tool.name: retrieval_tool}
         for t in extra_tools:
@@ -134,9 +139,11 @@ class LLMAgent:
 
     async def _decide_retrieval_node(self, state: AgentState) -> AgentState:
         logger.info("Deciding if transaction retrieval is needed")
+        extra = {"logprobs": True} if self.decide_logprobs else {}
         result = await self.llm.agenerate(self.decide_messages(state), tools=self.bound_tools,
                                           temperature=self.temperature, max_tokens=self.max_decide_tokens,
-                                          purpose="decide", ephemeral_kv=bool(state["tool_results"]))
+                                          purpose="decide", ephemeral_kv=bool(state["tool_results"]), **extra)
+        self._record_confidence(result)
         logger.info(f"Decide Retrieval Response: {result.text!r} tool_calls={[t.to_dict() for t in result.tool_calls]}")
         if result.tool_calls:
             tc = result.tool_calls[0]  # only the first call is honoured (llm_agent.py:100)
@@ -145,6 +152,21 @@ class LLMAgent:
         else:
             logger.info("LLM decided no retrieval needed")
         return state
+
+    def _record_confidence(self, result) -> None:
+        """exp(mean log-probability of the decide call's sampled tokens): the geometric-mean token
+        probability of the routing decision.  A decide that sampled nothing (scripted) records nothing."""
+        mean = getattr(result, "mean_logprob", None)
+        if not self.decide_logprobs or mean is None or mean != mean:
+            return
+        import math
+        from ..utils.metrics import METRICS
+        conf = math.exp(min(mean, 0.0))
+        METRICS.inc("decide_confidence_sum", conf)
+        METRICS.inc("decide_confidence_count")
+        if conf < self.decide_confidence_threshold:
+            METRICS.inc("decide_low_confidence")
+        logger.debug(f"decide confidence {conf:.4f} (mean logprob {mean:.4f})")
 
     async def _retrieve_data_node(self, state: AgentState) -> AgentState:
         logger.info("Retrieving transaction data")

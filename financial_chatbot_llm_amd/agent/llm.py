@@ -30,6 +30,16 @@ class LLMResult:
     tool_calls: List[ToolCall] = field(default_factory=list)
     prompt_tokens: int = 0
     completion_tokens: int = 0
+    # agenerate(..., logprobs=True): per generated token, log p of the token under the model's raw
+    # distribution (natural log; None where the token was appended without a sample), and the mean
+    # over the entries that carry one (None when none does)
+    logprobs: Optional[List[Optional[float]]] = None
+    mean_logprob: Optional[float] = None
+
+
+def mean_logprob(logprobs: Optional[Sequence[Optional[float]]]) -> Optional[float]:
+    vals = [v for v in (logprobs or ()) if v is not None]
+    return sum(vals) / len(vals) if vals else None
 
 
 class LLMBackend:

@@ -756,6 +756,49 @@ def bench_constrained_sample(dev, Ms=(16, 64, 128, 256), V: int = 128256, K: int
     return out
 
 
+def bench_lm_head_sample_logprob(dev, Ms=(16, 64, 128, 256), V: int = 128256, K: int = 4096) -> List[Dict]:
+    """Generation log-probabilities (vocab 128256, K 4096), three variants timed in interleaved rounds:
+    (a) the fused LM head + sampler as decode runs it, (b) its log-probability form
+    (ops.lm_head_sample_logprob: same tokens plus log softmax at them), (c) what a step without (b)
+    would pay: the LM-head logits GEMM + ops.sample + ops.token_logprobs.  price = (b) - (a).  Below
+    128 rows (the streaming kernel) (a) and (b) are also timed on the fragment-tiled copy of W, which
+    is what a model that keeps one streams."""
+    from ..ops import gemm
+    gemm.load_gemm_tuning("llama3-8b")
+    out = []
+    w = torch.randn((V, K), device=dev).to(torch.bfloat16) * 0.02
+    wt = gemm.tile_weight(w)
+    for M in Ms:
+        x = torch.randn((M, K), device=dev).to(torch.bfloat16)
+        temps = torch.full((M,), 0.7, device=dev)
+        sd = torch.arange(M, dtype=torch.int64, device=dev) * 977
+
+        def unfused():
+            logits = gemm.linear(x, w)
+            return ops.token_logprobs(logits, ops.sample(logits, temps, sd))
+        fns = {"fused": lambda: ops.lm_head_sample(x, w, temps, sd),
+               "fused_lp": lambda: ops.lm_head_sample_logprob(x, w, temps, sd),
+               "unfused_lp": unfused}
+        stream = M < ops.sampling.FUSED_LM_HEAD_MIN_M
+        if stream:
+            fns["fused_tiled"] = lambda: ops.lm_head_sample(x, w, temps, sd, wt=wt)
+            fns["fused_lp_tiled"] = lambda: ops.lm_head_sample_logprob(x, w, temps, sd, wt=wt)
+        r = interleaved(fns, rounds=9, iters=50)
+        ids, _ = ops.lm_head_sample_logprob(x, w, temps, sd)
+        out.append({"op": "lm_head_sample_logprob", "M": M, "V": V, "K": K,
+                    "kernel": "stream" if stream else "tile",
+                    **({"fused_tiled_us": round(r["fused_tiled"], 1),
+                        "fused_logprob_tiled_us": round(r["fused_lp_tiled"], 1)} if stream else {}),
+                    "fused_us": round(r["fused"], 1), "fused_logprob_us": round(r["fused_lp"], 1),
+                    "logits_sample_token_logprobs_us": round(r["unfused_lp"], 1),
+                    "price_us": round(r["fused_lp"] - r["fused"], 1),
+                    "price_pct": round(100.0 * (r["fused_lp"] / r["fused"] - 1.0), 1),
+                    "fused_lp_not_slower_than_unfused": bool(r["fused_lp"] <= r["unfused_lp"]),
+                    "same_tokens": bool(torch.equal(ids, ops.lm_head_sample(x, w, temps, sd)))})
+        print(json.dumps(out[-1]), flush=True)
+    return out
+
+
 def bench_bge_query(dev) -> List[Dict]:
     """bge-base encoder latency on retrieval-size query batches (the per-turn critical path): the
     four projections on hipBLASLt (+ the GELU pass) vs the tile kernel with the bias / bias+GELU
@@ -1800,6 +1843,9 @@ def main(argv=None) -> int:
                 "shard_shapes_tp8": lambda d: bench_shard_shapes(d, [n for n in SHARD_SHAPES if "tp8" in n]),
                 "shard_shapes_tp1": lambda d: bench_shard_shapes(d, [n for n in SHARD_SHAPES if "tp1" in n]),
                 "constrained_sample": bench_constrained_sample,
+                "lm_head_sample_logprob": bench_lm_head_sample_logprob,
+                "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
+                    d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),
                 "lm_head_stream_shard": lambda d: bench_lm_head_stream(d, V=16128, Ms=(1, 8, 32, 64, 127))}[name](dev)
     for r in res:

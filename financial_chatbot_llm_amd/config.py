@@ -257,6 +257,11 @@ class ServingConfig:
     ingest_token: Optional[str] = None
     # decide calls sample under the tool-call token automaton (schema-valid output); off by default
     constrain_toolcalls: bool = False
+    # the agent's decide call asks for the sampled tokens' log-probabilities and records
+    # exp(mean log-probability) per decide in the metrics registry (decide_confidence_sum / _count,
+    # decide_low_confidence below the threshold); off by default
+    decide_logprobs: bool = False
+    decide_confidence_threshold: float = 0.5
 
     @classmethod
     def from_env(cls, **overrides) -> "ServingConfig":
@@ -270,6 +275,8 @@ class ServingConfig:
             tools=_env_bool("PENNY_TOOLS", True),
             ingest_token=_env("PENNY_INGEST_TOKEN", "") or None,
             constrain_toolcalls=_env_bool("PENNY_CONSTRAIN_TOOLCALLS", False),
+            decide_logprobs=_env_bool("PENNY_DECIDE_LOGPROBS", False),
+            decide_confidence_threshold=float(_env("PENNY_DECIDE_CONFIDENCE_THRESHOLD", "0.5")),
         )
         return dataclasses.replace(c, **overrides)
 

@@ -133,4 +133,14 @@ __device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
   }
 }
 
+// better() that also carries the winner's raw logit l (the log-probability forms of the samplers):
+// same comparison, so the (bv, bi) it leaves are better()'s bit for bit
+__device__ __forceinline__ void better_lp(float& bv, int& bi, float& bl, float v, int i, float l) {
+  if (v > bv || (v == bv && i < bi)) {
+    bv = v;
+    bi = i;
+    bl = l;
+  }
+}
+
 #define PENNY_RETURN_LAUNCH() return (int)hipGetLastError()

@@ -18,6 +18,10 @@
 //   EPI_LOGPROB the LM head fused with prompt scoring (EPI_SAMPLE's sibling): per (token row, wave
 //             half) the max, sum of exp(l - max), target logit and argmax of the bf16-rounded logits;
 //             lm_logprob_final_kernel merges a row's partials to log softmax at the target token
+//   EPI_SAMPLE_LP EPI_SAMPLE that also reports the sampled token's log-probability: the same pick
+//             (score, noise, tie-break), plus per (token row, wave half) the raw logit of the chosen
+//             candidate and EPI_LOGPROB's (max, sum of exp(l - max)) of the raw bf16 logits;
+//             lm_sample_logprob_final_kernel merges them to the token and log softmax at it
 //   EPI_ROPE  the fused QKV projection (K3+K4+K5): a wave's 128 output columns are exactly one
 //             head, so the rotate-half RoPE pair (d, d+64) sits in one lane (accumulators f, f+4);
 //             q heads -> rotated q [M, Hq, 128]; k heads -> rotated, v heads -> as is, both
@@ -72,7 +76,7 @@ constexpr int GM = 4;                // token tiles per L2 group (r5 sweep of 1-
 enum { H_W0 = 0, H_X0 = 1, H_X1 = 2, H_W1 = 3 };
 enum { EPI_BF16 = 0, EPI_SILU = 1, EPI_SLAB = 2, EPI_RESID = 3, EPI_ROPE = 4, EPI_BIAS = 5, EPI_BIAS_GELU = 6,
        EPI_MOE_SILU = 7, EPI_MOE_ROUTE = 8, EPI_SAMPLE = 9, EPI_MOE_SILU_MX = 10, EPI_MOE_ROUTE_MX = 11,
-       EPI_LOGPROB = 12 };
+       EPI_LOGPROB = 12, EPI_SAMPLE_LP = 13 };
 
 // Grouped fp8 MoE GEMM (penny_moe_gemm_prefill_fp8): rows sorted by expert, bucket bounds on the
 // DEVICE (offsets [E+1]), so tiles are found without a host round trip.
@@ -107,6 +111,8 @@ struct SampleArgs {
 // EPI_LOGPROB: targets [M] (global token id, < 0: none); pm / ps / pt / pa [M, 2 * N / 256] partial
 // (max, sum of exp(l - max), target logit, argmax id) of each (row, wave half of 128 columns).
 // voff / vvalid as in SampleArgs.
+// EPI_SAMPLE_LP takes SampleArgs for the pick and borrows pm / ps / pt from here: pt holds the raw
+// logit of each partial's chosen candidate (targets / pa unused).
 struct LogprobArgs {
   const int* targets;
   float* pm;
@@ -300,7 +306,10 @@ __global__ void __launch_bounds__(512) gemm_prefill_kernel(const void* __restric
 
   // ---- tile of this workgroup: bijective XCD remap, then L2 groups of GM token tiles ----
   const int Mt = (M + TM - 1) / TM + (FP8 ? ma.E : 0), Nt = N / TN, tiles = Mt * Nt;
-  const bool tail = !FP8 && ta.s > 1 && (int)blockIdx.x >= ta.dpn;   // workgroup-uniform
+  // EPI_SAMPLE_LP is only launched whole-tile (penny_lm_head_sample_logprob passes no TailArgs): the
+  // tail's combine pass holds 256 VGPRs of accumulators and partials, and compiled in it costs this
+  // epilogue's lane ids a spill
+  const bool tail = !FP8 && EPI != EPI_SAMPLE_LP && ta.s > 1 && (int)blockIdx.x >= ta.dpn;   // workgroup-uniform
   int s = 0, tile, tu = 0, tj = 0;
   if (tail) {
     const int u = blockIdx.x - ta.dpn;        // tail workgroups are dispatched last, round robin
@@ -739,6 +748,52 @@ __global__ void __launch_bounds__(512) gemm_prefill_kernel(const void* __restric
         const long slot = (long)m * (2 * Nt) + 2 * tn + wa;
         sa.pv[slot] = bv;
         sa.pi[slot] = bi;
+      }
+    } else if constexpr (EPI == EPI_SAMPLE_LP) {
+      // EPI_SAMPLE's pick, carrying the winner's raw logit, and the half's max raw logit in the same
+      // pass; then EPI_LOGPROB's second pass over acc for the sum of exp against the reduced max
+      const float temp = sa.temps[m];
+      const bool greedy = !(temp > 0.f);
+      const float inv_t = greedy ? 1.f : 1.f / temp;
+      const unsigned long long seed = sa.seeds[m];
+      const int loc0 = n0 + wa * 128 + 4 * g;
+      float bv = -INFINITY, bl = -INFINITY, mx = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int f = 0; f < 8; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int loc = loc0 + f * 16 + r, idx = sa.voff + loc;
+          const float l = (float)(bf16)acc[f][t][r];    // the bf16 logit the unfused path samples
+          float v = l;
+          if (!greedy) v = v * inv_t + gumbel_noise(seed, idx);
+          if (loc >= sa.vvalid) v = -INFINITY;
+          else mx = fmaxf(mx, l);
+          better_lp(bv, bi, bl, v, idx, l);
+        }
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        const float ol = __shfl_xor(bl, o, 64);
+        better_lp(bv, bi, bl, ov, oi, ol);
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      }
+      float ps = 0.f;
+#pragma unroll
+      for (int f = 0; f < 8; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (loc0 + f * 16 + r < sa.vvalid) ps += __expf((float)(bf16)acc[f][t][r] - mx);
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) ps += __shfl_xor(ps, o, 64);
+      if (g == 0) {
+        const long slot = (long)m * (2 * Nt) + 2 * tn + wa;
+        sa.pv[slot] = bv;
+        sa.pi[slot] = bi;
+        la.pt[slot] = bl;
+        la.pm[slot] = mx;
+        la.ps[slot] = ps;
       }
     } else if constexpr (EPI == EPI_LOGPROB) {
       // the log-likelihood sibling of EPI_SAMPLE, same lane set per row: the wave half's max / argmax
@@ -1268,5 +1323,96 @@ PENNY_API int penny_lm_head_logprob(const void* X, int ldx, const void* W, int K
                      nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, SampleArgs{}, TailArgs{},
                      la);
   hipLaunchKernelGGL(lm_logprob_final_kernel, dim3(M), dim3(256), 0, stream, pm, ps, pt, pa, P, stats, logprob);
+  return (int)hipGetLastError();
+}
+
+// Reduce a row's partials of the LM head fused with sampling and log-probabilities (EPI_SAMPLE_LP,
+// SK_SAMPLE_LP): the token exactly as lm_sample_final_kernel picks it, its raw logit lc from the
+// partial that won, and Mx / S merged as lm_logprob_final_kernel merges them (partials without a
+// valid column, ps == 0, skipped): out[row] = token, logprob[row] = lc - Mx - log S.
+__global__ void __launch_bounds__(256) lm_sample_logprob_final_kernel(
+    const float* __restrict__ pv, const int* __restrict__ pi, const float* __restrict__ pl,
+    const float* __restrict__ pm, const float* __restrict__ ps, int P, int* __restrict__ out,
+    float* __restrict__ logprob) {
+  __shared__ float sv[4], sl[4], sm[4], ss[4];
+  __shared__ int si[4];
+  const long row = blockIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float bv = -INFINITY, bl = -INFINITY, mx = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int j = threadIdx.x; j < P; j += 256) {
+    better_lp(bv, bi, bl, pv[row * P + j], pi[row * P + j], pl[row * P + j]);
+    mx = fmaxf(mx, pm[row * P + j]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    const float ol = __shfl_xor(bl, o, 64);
+    better_lp(bv, bi, bl, ov, oi, ol);
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  }
+  if (lane == 0) {
+    sv[w] = bv;
+    si[w] = bi;
+    sl[w] = bl;
+    sm[w] = mx;
+  }
+  __syncthreads();
+  bv = sv[0], bi = si[0], bl = sl[0], mx = sm[0];
+  for (int k = 1; k < 4; ++k) {
+    better_lp(bv, bi, bl, sv[k], si[k], sl[k]);
+    mx = fmaxf(mx, sm[k]);
+  }
+  float s = 0.f;
+  for (int j = threadIdx.x; j < P; j += 256) {
+    const float p = ps[row * P + j];
+    if (p != 0.f) s += p * __expf(pm[row * P + j] - mx);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) ss[w] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+    out[row] = bi;
+    logprob[row] = bl - mx - logf(s);
+  }
+}
+
+// the merge alone (gemm_splitk.hip's streaming form shares it): partial arrays [M, P] row-major
+PENNY_API int penny_lm_sample_logprob_final(const float* pv, const int* pi, const float* pl, const float* pm,
+                                            const float* ps, int P, int M, int* out, float* logprob,
+                                            hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (!pv || !pi || !pl || !pm || !ps || P <= 0 || !out || !logprob) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(lm_sample_logprob_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, pl, pm, ps, P, out,
+                     logprob);
+  return (int)hipGetLastError();
+}
+
+// penny_lm_head_sample_shard's inputs with a whole vocabulary's outputs: out [M] int32 = the token
+// the plain kernel samples (bit for bit) and logprob [M] f32 = log softmax of the row's raw
+// bf16-rounded logits (temperature 1, valid columns only) at that token.  workspace: 5 * M * 2 * (Vpad / 256) 4-byte words.
+// Contract (checked): Vpad % 256 == 0, 0 < vvalid <= Vpad, voff >= 0, K % 64 == 0, ldx % 8 == 0.
+PENNY_API int penny_lm_head_sample_logprob(const void* X, int ldx, const void* W, int K, int M, int Vpad, int vvalid,
+                                           int voff, const float* temps, const unsigned long long* seeds,
+                                           void* workspace, int* out, float* logprob, hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (Vpad % TN || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % BK || ldx % 8 || !temps || !seeds ||
+      !workspace || !out || !logprob)
+    return (int)hipErrorInvalidValue;
+  const int P = 2 * (Vpad / TN);
+  float* pv = static_cast<float*>(workspace);
+  int* pi = reinterpret_cast<int*>(pv + (long)M * P);
+  float* pl = pv + 2 * (long)M * P;
+  float* pm = pl + (long)M * P;
+  float* ps = pm + (long)M * P;
+  const SampleArgs sa{temps, seeds, pv, pi, voff, vvalid};
+  const LogprobArgs la{nullptr, pm, ps, pl, nullptr, voff, vvalid};
+  hipLaunchKernelGGL((gemm_prefill_kernel<EPI_SAMPLE_LP>), grid_for(M, Vpad, 1), dim3(512), 0, stream, X, ldx, W, K,
+                     nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{}, la);
+  hipLaunchKernelGGL(lm_sample_logprob_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, pl, pm, ps, P, out,
+                     logprob);
   return (int)hipGetLastError();
 }

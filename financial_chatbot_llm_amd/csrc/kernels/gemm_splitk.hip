@@ -40,11 +40,13 @@ union Frag {
 };
 
 // epilogues of splitk_gemm_kernel
-enum { SK_SLAB = 0, SK_SILU = 1, SK_BF16 = 2, SK_SAMPLE = 3 };
+enum { SK_SLAB = 0, SK_SILU = 1, SK_BF16 = 2, SK_SAMPLE = 3, SK_SAMPLE_LP = 4 };
 
 // SK_SAMPLE (the streaming LM head + K12 sampler): per-row temperature (<= 0: greedy) and seed;
 // pv / pi [M, pstride] partial (best score, token) per (row, workgroup tile, wave row).  Token
 // ids are voff + local row; local rows >= vvalid (a vocab shard's padding) never win.
+// SK_SAMPLE_LP: pv / pi are the first two of five contiguous [M, pstride] planes; the other three
+// take the chosen candidate's raw logit, the wave's max raw logit and its sum of exp(l - max).
 struct SkSample {
   const float* temps;
   const unsigned long long* seeds;
@@ -142,6 +144,9 @@ __device__ __forceinline__ void stage_mma(const char* __restrict__ base, f32x4 (
 //             reduced per row by lm_sample_final_kernel (gemm_prefill.hip).  The weight-streaming LM
 //             head for decode batches (M <= 128), where the 256x256 tile kernel is MFMA-bound on
 //             padding rows.
+//   SK_SAMPLE_LP SK_SAMPLE that also leaves, per (row, wave), the chosen candidate's raw logit and the
+//             (max, sum of exp(l - max)) of the wave's raw logits: the same token, plus its
+//             log-probability after lm_sample_logprob_final_kernel (gemm_prefill.hip).
 // WROW: W is the plain row-major [N, K] weight (no fragment-tiled copy): its stage pieces are
 // 8 rows x 128 B with the same source-side XOR swizzle as X, so every glds instruction still reads
 // whole 128-B lines and the fragment reads stay conflict-free.
@@ -178,7 +183,7 @@ __global__ void __launch_bounds__(256, 1) splitk_gemm_kernel(const bf16* __restr
   M = min(Mtot - m0, 16 * MT);
   X += (long)m0 * ldx;
   if constexpr (EPI == SK_SILU || EPI == SK_BF16) Y += (long)m0 * ldy;
-  PENNY_DASSERT(M > 0 && (EPI != SK_SAMPLE || gridDim.y == 1));
+  PENNY_DASSERT(M > 0 && ((EPI != SK_SAMPLE && EPI != SK_SAMPLE_LP) || gridDim.y == 1));
   PENNY_DASSERT((tile + 1) * 16 * NF <= N && K % (64 * BKM * S) == 0);
   const int n0 = tile * 16 * NF;
   const int kc = K / S, k0 = s * kc;
@@ -322,6 +327,64 @@ __global__ void __launch_bounds__(256, 1) splitk_gemm_kernel(const bf16* __restr
     }
     return;
   }
+  if constexpr (EPI == SK_SAMPLE_LP) {
+    // SK_SAMPLE's pick carrying the winner's raw logit, with the wave's max raw logit in the same
+    // pass and a second pass over acc for the sum of exp against the reduced max (the tile kernel's
+    // EPI_SAMPLE_LP on this kernel's lane set)
+    const long plane = (long)Mtot * sa.pstride;
+    float* pl = sa.pv + 2 * plane;
+    float* pm = pl + plane;
+    float* pe = pm + plane;
+#pragma unroll
+    for (int t = 0; t < TW; ++t) {
+      const int m = (wb * TW + t) * 16 + col;
+      if (m >= M) continue;
+      const float temp = sa.temps[m];
+      const bool greedy = !(temp > 0.f);
+      const float inv_t = greedy ? 1.f : 1.f / temp;
+      const unsigned long long seed = sa.seeds[m];
+      const int loc0 = n0 + wa * FW * 16 + 4 * g;
+      float bv = -INFINITY, bl = -INFINITY, mx = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int f = 0; f < FW; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int loc = loc0 + f * 16 + r, idx = sa.voff + loc;
+          const float l = (float)(bf16)acc[f][t][r];   // the bf16 logit the unfused path samples
+          float v = l;
+          if (!greedy) v = v * inv_t + gumbel_noise(seed, idx);
+          if (loc >= sa.vvalid) v = -INFINITY;
+          else mx = fmaxf(mx, l);
+          better_lp(bv, bi, bl, v, idx, l);
+        }
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        const float ol = __shfl_xor(bl, o, 64);
+        better_lp(bv, bi, bl, ov, oi, ol);
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      }
+      float se = 0.f;
+#pragma unroll
+      for (int f = 0; f < FW; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (loc0 + f * 16 + r < sa.vvalid) se += __expf((float)(bf16)acc[f][t][r] - mx);
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) se += __shfl_xor(se, o, 64);
+      if (g == 0) {
+        const long slot = (long)m * sa.pstride + tile * WA + wa;
+        sa.pv[slot] = bv;
+        sa.pi[slot] = bi;
+        pl[slot] = bl;
+        pm[slot] = mx;
+        pe[slot] = se;
+      }
+    }
+    return;
+  }
   // lane holds W rows n = 16f + 4g + r (r = 0..3) for token 16t + col: one 16-B store per tile
   float* ps = P + (long)s * Mtot * N + (long)m0 * N;
 #pragma unroll
@@ -417,12 +480,12 @@ int launch_bf16(const void* X, int ldx, const void* Wt, int K, void* Y, int ldy,
 
 // the streaming LM head: row-major W (wrow) or its fragment-tiled copy; ring budget 150 KiB (one
 // workgroup per CU) or 72 KiB (two)
-template <int NF, int MT, int WA>
+template <int NF, int MT, int WA, int EPI = SK_SAMPLE>
 int launch_sample(const void* X, int ldx, const void* Wt, int K, int M, int N, int wrow, int ring2, const SkSample& sa,
                   hipStream_t st) {
   const dim3 grid(N / (16 * NF)), block(256);
 #define SK_SAMPLE_LAUNCH(WROW_, KB_)                                                                               \
-  hipLaunchKernelGGL((splitk_gemm_kernel<NF, MT, WA, SK_SAMPLE, WROW_, KB_, 16>), grid, block, 0, st, (const bf16*)X, ldx, \
+  hipLaunchKernelGGL((splitk_gemm_kernel<NF, MT, WA, EPI, WROW_, KB_, 16>), grid, block, 0, st, (const bf16*)X, ldx, \
                      (const bf16*)Wt, K, (float*)nullptr, M, N, 1, (bf16*)nullptr, 0, sa)
   // the 72-KiB ring only where it still holds >= 3 stages (else the 150-KiB one)
   constexpr bool R2 = Ring<NF, MT, 72, 16>::NBUF >= 3;
@@ -624,4 +687,45 @@ PENNY_API int penny_lm_head_stream_sample(const void* X, int ldx, const void* W,
 #undef LS_CASE
   if (rc) return rc;
   return penny_lm_sample_final(pv, pi, pstride, M, out, pairs, stream);
+}
+
+// lm_sample_logprob_final_kernel's launcher (gemm_prefill.hip)
+extern "C" int penny_lm_sample_logprob_final(const float* pv, const int* pi, const float* pl, const float* pm,
+                                             const float* ps, int P, int M, int* out, float* logprob,
+                                             hipStream_t stream);
+
+// penny_lm_head_stream_sample with the sampled token's log-probability: out [M] int32 = the token the
+// plain kernel samples (bit for bit), logprob [M] f32 = log softmax of the row's raw bf16-rounded
+// logits (temperature 1, valid columns only) at it.  workspace >= 5 * M * (Vpad / (16*nf)) * 2 words.
+// Contract (checked): as penny_lm_head_stream_sample, out and logprob both required.
+PENNY_API int penny_lm_head_stream_sample_logprob(const void* X, int ldx, const void* W, int K, int M, int Vpad,
+                                                  int vvalid, int voff, const float* temps,
+                                                  const unsigned long long* seeds, void* workspace, int* out,
+                                                  float* logprob, int nf, int wrow, int ring2, hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (M > 128 || (nf != 4 && nf != 8) || Vpad % (16 * nf) || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % 64 ||
+      ldx % 8 || !temps || !seeds || !workspace || !out || !logprob)
+    return (int)hipErrorInvalidValue;
+  const int tiles = Vpad / (16 * nf), mt = (M + 15) / 16;
+  const int wa = nf == 8 ? 2 : (mt <= 2 || (mt > 4 && mt <= 6) ? 2 : 1);
+  const int pstride = tiles * wa;
+  const long plane = (long)M * pstride;
+  float* pv = static_cast<float*>(workspace);
+  int* pi = reinterpret_cast<int*>(pv + plane);
+  const SkSample sa{temps, seeds, pv, pi, pstride, voff, vvalid};
+  int rc;
+#define LS_CASE(MT_, WA4_)                                                                                      \
+  if (mt <= MT_) {                                                                                              \
+    if (nf == 4) rc = launch_sample<4, MT_, WA4_, SK_SAMPLE_LP>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream); \
+    else rc = launch_sample<8, MT_, 2, SK_SAMPLE_LP>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream);            \
+  } else
+  LS_CASE(2, 2)
+  LS_CASE(4, 1)
+  LS_CASE(6, 2)
+  LS_CASE(8, 1)
+  return (int)hipErrorInvalidValue;
+#undef LS_CASE
+  if (rc) return rc;
+  return penny_lm_sample_logprob_final(pv, pi, pv + 2 * plane, pv + 3 * plane, pv + 4 * plane, pstride, M, out,
+                                       logprob, stream);
 }

@@ -486,3 +486,75 @@ PENNY_API int penny_topk_topp_threshold(const void* logits, int is_fp32, long ro
   }
   PENNY_RETURN_LAUNCH();
 }
+
+// Log-probability of one chosen token per row of logits the step already holds (top-k / top-p rows,
+// constrained rows, the unfused LM head): logprob[row] = log softmax(l)[ids[row]] over the raw
+// logits at temperature 1 -- what the fused LM heads' log-probability forms report.  One pass: every
+// thread keeps an online (max, sum of exp(l - max)) over its 8-logit chunks, merged across the
+// 1024-thread workgroup; then the gather.  -inf logits add nothing, a NaN logit makes the row NaN,
+// and an id outside [0, V) reports NaN without a read.
+__device__ __forceinline__ float lse_scale(float from, float to) { return from == to ? 1.f : __expf(from - to); }
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+  const float nm = fmaxf(m, om);
+  s = s * lse_scale(m, nm) + os * lse_scale(om, nm);
+  m = nm;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) token_logprob_kernel(const T* __restrict__ logits, long row_stride,
+                                                             const int* __restrict__ ids,
+                                                             float* __restrict__ logprob, int V) {
+  __shared__ float sm[16], ss[16];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const T* lr = logits + row * row_stride;
+  float m = -INFINITY, s = 0.f;
+  const int nch = V >> 3;
+  for (int c = tid; c < nch; c += 1024) {
+    float f[8];
+    load8<T>(lr + c * 8, f);
+    float cm = f[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) cm = fmaxf(cm, f[k]);
+    const float nm = fmaxf(m, cm);          // fmaxf drops a NaN: it reaches s through its exp below
+    s *= lse_scale(m, nm);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += f[k] == -INFINITY ? 0.f : __expf(f[k] - nm);
+    m = nm;
+  }
+  for (int loc = (V & ~7) + tid; loc < V; loc += 1024) {   // tail (V not a multiple of 8)
+    const float l = (float)lr[loc];
+    const float nm = fmaxf(m, l);
+    s = s * lse_scale(m, nm) + (l == -INFINITY ? 0.f : __expf(l - nm));
+    m = nm;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+    lse_merge(m, s, om, os);
+  }
+  if (lane == 0) {
+    sm[wid] = m;
+    ss[wid] = s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w) lse_merge(m, s, sm[w], ss[w]);
+    const int id = ids[row];
+    logprob[row] = id >= 0 && id < V ? (float)lr[id] - m - logf(s) : NAN;
+  }
+}
+
+// logits [B, V] bf16 / f32 with 16-B aligned rows (as penny_sample), ids [B] int32 -> logprob [B] f32.
+PENNY_API int penny_token_logprob(const void* logits, int is_fp32, long row_stride, const int* ids, float* logprob,
+                                  int B, int V, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!logits || !ids || !logprob || V <= 0) return (int)hipErrorInvalidValue;
+  if (is_fp32) {
+    hipLaunchKernelGGL(token_logprob_kernel<float>, dim3(B), dim3(1024), 0, stream, (const float*)logits, row_stride,
+                       ids, logprob, V);
+  } else {
+    hipLaunchKernelGGL(token_logprob_kernel<bf16>, dim3(B), dim3(1024), 0, stream, (const bf16*)logits, row_stride,
+                       ids, logprob, V);
+  }
+  PENNY_RETURN_LAUNCH();
+}

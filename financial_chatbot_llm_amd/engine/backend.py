@@ -29,7 +29,7 @@ import os
 from typing import AsyncIterator, Callable, Optional, Sequence
 
 from ..agent.grammar import ToolCallGrammar, jump_mask
-from ..agent.llm import LLMBackend, LLMResult
+from ..agent.llm import LLMBackend, LLMResult, mean_logprob
 from ..agent.toolcall import parse_tool_calls
 from ..tools.base import Tool
 from ..utils.profiling import marker
@@ -60,6 +60,7 @@ class EngineLLM(LLMBackend):
         # tool-call language; off by default (PENNY_CONSTRAIN_TOOLCALLS=1 / ServingConfig)
         self.constrain_tools = bool(constrain_tools) and self._can_constrain()
         self.fsm_max_states = fsm_max_states
+        self._logprobs_ok: Optional[bool] = None     # decided (and warned about) at the first request
         self.respond_ignore_eos = respond_ignore_eos
         self.respond_tokens = respond_tokens
         self.stream_chunk_tokens = max(1, stream_chunk_tokens)
@@ -99,6 +100,23 @@ class EngineLLM(LLMBackend):
                                          "without CP; decide calls decode unconstrained")
             return False
         return True
+
+    def _can_logprob(self) -> bool:
+        """``LLMEngine.add_request`` refuses log-probabilities under TP / CP; there the switch is
+        dropped with one warning and results carry ``logprobs=None``."""
+        if self._logprobs_ok is None:
+            core = getattr(self.engine, "engine", None)
+            cfg = getattr(core, "cfg", None) or getattr(self.engine, "cfg", None)
+            ps = getattr(core, "ps", None)
+            refused = (getattr(cfg, "tp_size", 1) > 1 or getattr(cfg, "cp_size", 1) > 1
+                       or getattr(ps, "tp_size", 1) > 1 or getattr(getattr(core, "model", None), "tp_size", 1) > 1
+                       or getattr(core, "cp", None) is not None)
+            if refused:
+                from ..utils.logging import get_logger
+                get_logger(__name__).warning("generation log-probabilities need a TP = 1 engine without CP; "
+                                             "results carry none")
+            self._logprobs_ok = not refused
+        return self._logprobs_ok
 
     def _constraint(self, tools):
         if not self.constrain_tools or not tools or self.decide_script is not None:
@@ -143,12 +161,14 @@ class EngineLLM(LLMBackend):
         params = SamplingParams(temperature=temperature, max_tokens=max_tokens, forced_output=forced,
                                 forced_jump=jump, grammar=grammar, constraint=self._constraint(tools),
                                 ephemeral_kv=bool(kw.get("ephemeral_kv")),
-                                prompt_lookup=self.prompt_lookup, priority_ts=TURN_START.get())
+                                prompt_lookup=self.prompt_lookup, priority_ts=TURN_START.get(),
+                                logprobs=bool(kw.get("logprobs")) and self._can_logprob())
         out = await self.engine.generate_all(ids, params)
         self._account(kw.get("purpose", "decide"), len(ids), out.seq)
         text = self.tok.decode(out.seq.output_ids)
+        lps = list(out.seq.output_logprobs) if params.logprobs else None
         return LLMResult(text=text, tool_calls=parse_tool_calls(text, tools), prompt_tokens=len(ids),
-                         completion_tokens=len(out.seq.output_ids))
+                         completion_tokens=len(out.seq.output_ids), logprobs=lps, mean_logprob=mean_logprob(lps))
 
     async def astream(self, messages, temperature=0.5, max_tokens=512, **kw) -> AsyncIterator[str]:
         n = self.respond_tokens or max_tokens

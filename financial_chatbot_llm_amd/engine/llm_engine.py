@@ -43,6 +43,9 @@ class StepOutput:
     finished: bool
     finish_reason: Optional[str]
     seq: Sequence
+    # parallel to new_token_ids when the request asked (SamplingParams.logprobs): the token's
+    # log-probability, None for a token appended without a sample; None when it did not ask
+    new_logprobs: Optional[List[Optional[float]]] = None
 
 
 @dataclass
@@ -183,6 +186,9 @@ class LLMEngine:
                     seq.fsm_off = self.runner.register_automaton(params.constraint)
                 except ValueError as e:            # tables full / other tokenizer: decode as before
                     logger.warning(f"request {request_id}: constraint dropped ({e}); decoding unconstrained")
+        if params.logprobs and (self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None):
+            raise NotImplementedError("generation log-probabilities: TP / CP engines sample vocabulary-parallel "
+                                      "[B, 2] pairs, which do not carry them yet")
         self.requests[request_id] = seq
         if self.cp is not None and self.cp.wants(seq):
             self.cp.queue.append(seq)          # prefilled context-parallel before the next step
@@ -485,13 +491,28 @@ class LLMEngine:
             return "length"
         return None
 
-    def _resolve(self, samplers: List[Sequence], sampled: List[int]) -> List[StepOutput]:
+    @staticmethod
+    def _emit(seq: Sequence, new: List[int], lps: List[Optional[float]], reason: Optional[str]) -> StepOutput:
+        """The StepOutput of ``new``; a request that asked for log-probabilities records ``lps``
+        (parallel to ``new``) beside its output."""
+        if not seq.params.logprobs:
+            return StepOutput(seq.request_id, new, reason is not None, reason, seq)
+        assert len(lps) == len(new)
+        seq.output_logprobs.extend(lps)
+        return StepOutput(seq.request_id, new, reason is not None, reason, seq, list(lps))
+
+    def _resolve(self, samplers: List[Sequence], sampled: List[int],
+                 logprobs: Optional[List[float]] = None) -> List[StepOutput]:
         now = time.perf_counter()
         outs: List[StepOutput] = []
-        for seq, _, toks in self._group(samplers, sampled):
+        for seq, row, toks in self._group(samplers, sampled):
             tok = toks[-1]
             if seq.finished:                   # aborted (or finished) while in flight
                 continue
+            # this sequence's rows of the step's log-probabilities (a step none of whose requests
+            # asked carries none)
+            rlp: List[Optional[float]] = (logprobs[row:row + len(toks)] if logprobs is not None
+                                          else [None] * len(toks))
             was_sampled = False
             sat_out = False                    # not in the step launched just now: may draft
             if seq.awaiting:
@@ -502,23 +523,28 @@ class LLMEngine:
                     self.bm.commit(seq)        # verified positions only (num_computed clamped)
                     seq.output_ids.append(bonus)
                     new = acc + [bonus]
+                    lps = self._verified_logprobs(seq, rlp, len(acc))
                     was_sampled = True
                 elif seq.jump_tail:
                     new = seq.jump_tail
                     seq.jump_tail = []
                     seq.output_ids.extend(new)
+                    lps = [None] * len(new)
                 else:
                     new = [int(tok)]
                     seq.output_ids.extend(new)
+                    lps = [rlp[-1]]
                     was_sampled = seq.params.forced_output is None
             elif seq.pending_src >= 0:
                 new = [int(tok)]
                 seq.output_ids[-1] = new[0]
                 seq.pending_src = -1
+                lps = [rlp[-1]]
                 was_sampled = True
             else:                              # known run, appended at launch time
                 new = seq.last_run or [seq.output_ids[-1]]
                 seq.last_run = []
+                lps = [None] * len(new)
             tok = new[-1]
             if seq.first_token_time is None:
                 seq.first_token_time = now
@@ -535,8 +561,18 @@ class LLMEngine:
                     if draft:                  # rides with the just-known token next step
                         seq.output_ids.extend(draft)
                         seq.spec_rows = len(draft) + 1
-            outs.append(StepOutput(seq.request_id, new, reason is not None, reason, seq))
+            outs.append(self._emit(seq, new, lps, reason))
         return outs
+
+    @staticmethod
+    def _verified_logprobs(seq: Sequence, rlp: List[Optional[float]], j: int) -> List[Optional[float]]:
+        """Log-probabilities of a verified chunk's j accepted draft tokens and its bonus token: an
+        accepted draft token IS the sample of its row, so rows 0 .. j are the tokens kept.  A
+        teacher-forced chunk is verified against the script, not against samples: its accepted
+        tokens carry None."""
+        if seq.params.forced_output is not None:
+            return [None] * j + [rlp[j]]
+        return list(rlp[:j + 1])
 
     def _step_overlap(self) -> List[StepOutput]:
         t0 = time.perf_counter()
@@ -572,7 +608,7 @@ class LLMEngine:
             with marker("engine.wait"):
                 res = prev[2].result()
             with marker("engine.resolve"):
-                outs = self._resolve(prev[1], res)
+                outs = self._resolve(prev[1], res, prev[2].logprobs)
         self._inflight = launched
         t3 = time.perf_counter()
         tm = self.timing
@@ -591,7 +627,9 @@ class LLMEngine:
         if self.ps.tp_size > 1:
             comm.broadcast_step(si)
         t1 = time.perf_counter()
-        sampled = self.runner.execute(si)
+        pending = self.runner.launch(si)
+        sampled = pending.result()
+        logprobs = pending.logprobs
         now = time.perf_counter()
         tm = self.timing
         tm["prepare_s"] += t1 - t0
@@ -602,13 +640,19 @@ class LLMEngine:
             seq.num_computed = start + n
         for seq in batch.decode:
             seq.num_computed = seq.num_tokens
-        for seq, _, toks in self._group(samplers, sampled):
+        for seq, row, toks in self._group(samplers, sampled):
             acc: List[int] = []
             tok = toks[-1]
+            rlp: List[Optional[float]] = (logprobs[row:row + len(toks)] if logprobs is not None
+                                          else [None] * len(toks))
+            lps: List[Optional[float]] = [rlp[-1]]
             if seq.spec_rows > 1:
                 acc, tok = self._verify(seq, toks)
+                lps = self._verified_logprobs(seq, rlp, len(acc))
             known = self._known_run(seq)
             run = known or [int(tok)]
+            if known:                           # the known run replaces the row's sample
+                lps = lps[:-1] + [None] * len(known)
             seq.output_ids.extend(run)
             if seq.first_token_time is None:
                 seq.first_token_time = now
@@ -620,6 +664,7 @@ class LLMEngine:
                     extra = extra[:max(seq.params.max_tokens - len(seq.output_ids), 0)]
                     seq.output_ids.extend(extra)
                     run = run + extra
+                    lps = lps + [None] * len(extra)
                     reason = self._finish_reason(seq, run[-1])
             self.bm.commit(seq)
             if reason is not None:
@@ -630,7 +675,7 @@ class LLMEngine:
                 if draft:
                     seq.output_ids.extend(draft)
                     seq.spec_rows = len(draft) + 1
-            outs.append(StepOutput(seq.request_id, acc + run, reason is not None, reason, seq))
+            outs.append(self._emit(seq, acc + run, lps, reason))
         for seq, start, n in batch.prefill:
             if start + n < seq.num_tokens:
                 self.bm.commit(seq)
@@ -744,6 +789,7 @@ class LLMEngine:
                 "scored_tokens": self.scored_tokens,
                 "constrained_tokens": self.runner.stats["constrained_tokens"],
                 "constrained_steps": self.runner.stats["constrained_steps"],
+                "logprob_steps": self.runner.stats["logprob_steps"],
                 "kv_dtype": self.kv.kv_dtype,
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),

@@ -61,6 +61,10 @@ class StepInputs:
     # >= 0 an explicit global state, -1 unconstrained, <= -2 carry row (-2 - v) of the previous
     # step's state_out (the row's last token is still on the device)
     fsm_state: Optional[np.ndarray] = None
+    # some sampled row's request asked for log-probabilities: the step samples through the
+    # log-probability form of whatever path it takes and every row's value rides back with the ids
+    # (rows that did not ask discard theirs).  Not on the C4 wire: TP / CP engines refuse the request.
+    want_logprobs: bool = False
 
     @property
     def num_prefill_tokens(self) -> int:
@@ -167,6 +171,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     cu = [0]
     ctx_p, tables_p = [], []
     logits_idx, temps, seeds, tk, tp, fsm = [], [], [], [], [], []
+    want_lp = False
     max_q = 0
     for seq, start, n in batch.prefill:
         np_ = len(seq.prompt_ids)
@@ -186,6 +191,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
             # a speculative chunk samples its last spec_rows positions (verification), others one
             r = sample_rows(seq, n)
             k0 = len(seq.output_ids) - r + 1
+            want_lp = want_lp or seq.params.logprobs
             for i in range(r):
                 logits_idx.append(cu[-1] - r + i)
                 temps.append(seq.params.temperature)
@@ -214,6 +220,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
         tk.append(seq.params.top_k)
         tp.append(seq.params.top_p)
         fsm.append(fsm_code(seq, len(seq.output_ids)))
+        want_lp = want_lp or seq.params.logprobs
 
     i32 = lambda x: np.asarray(x, np.int32)  # noqa: E731
     cat = lambda parts, tail: np.concatenate(parts + [i32(tail)]) if parts else i32(tail)  # noqa: E731
@@ -225,7 +232,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     return StepInputs(cat(ids_parts, ids_d), cat(pos_parts, pos_d), cat(slot_parts, slots_d), i32(cu), i32(ctx_p),
                       _table(tables_p), max_q, i32(ctx_d), bt_d, np.asarray(logits_idx, np.int64),
                       np.asarray(temps, np.float32), np.asarray(seeds, np.int64), i32(tk), np.asarray(tp, np.float32),
-                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None)
+                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None, bool(want_lp))
 
 
 def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
@@ -246,17 +253,24 @@ class CollectiveTimeout(RuntimeError):
 
 
 class PendingStep:
-    """Sampled ids of a launched step (host copy in flight)."""
+    """Sampled ids of a launched step (host copy in flight).  A step that sampled with
+    log-probabilities carries them in the same host buffer, ``lp_off`` int32 slots in (f32 bits), or
+    in ``cpu_lp`` on the CPU: ``result()`` leaves them in ``logprobs`` ([n] floats, else None)."""
 
     def __init__(self, cpu_out: Optional[torch.Tensor], n: int, host: Optional[torch.Tensor], event,
-                 start_event=None, stats: Optional[Dict] = None, key: str = "", check_err: bool = False):
+                 start_event=None, stats: Optional[Dict] = None, key: str = "", check_err: bool = False,
+                 lp_off: int = -1, cpu_lp: Optional[torch.Tensor] = None):
         self._cpu, self.n, self._host, self._event = cpu_out, n, host, event
         self._start, self._stats, self._key = start_event, stats, key
         self._check_err = check_err
+        self._lp_off, self._cpu_lp = lp_off, cpu_lp
+        self.logprobs: Optional[List[float]] = None
 
     def result(self) -> List[int]:
         if self.n == 0:
             return []
+        if self._cpu_lp is not None:
+            self.logprobs = self._cpu_lp.tolist()
         if self._cpu is not None:
             return self._cpu.tolist()
         if self._event is not None:
@@ -275,15 +289,19 @@ class PendingStep:
         if self._check_err and int(self._host[self.n]):
             raise CollectiveTimeout("custom all-reduce: a TP peer missed the bounded wait; this step's "
                                     "hidden states are stale")
+        if self._lp_off >= 0:
+            self.logprobs = self._host[self._lp_off:self._lp_off + self.n].view(torch.float32).tolist()
         return self._host[:self.n].tolist()
 
 
 class _DecodeGraph:
     def __init__(self, graph, B: int, out: torch.Tensor, fused: bool = False,
-                 state_out: Optional[torch.Tensor] = None):
+                 state_out: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None):
         # fused: the graph samples inside the LM head (no top-k / top-p support)
         # state_out: the constrained twin's next automaton states (beside ``out``)
+        # logprob: a log-probability twin's [B] f32 values (beside ``out``)
         self.graph, self.B, self.out, self.fused, self.state_out = graph, B, out, fused, state_out
+        self.logprob = logprob
 
 
 class ModelRunner:
@@ -323,12 +341,18 @@ class ModelRunner:
         self._step_state_out: Optional[torch.Tensor] = None
         self.graphs_fsm: Dict[int, _DecodeGraph] = {}     # constrained twins of the decode buckets (lazy)
         self._fsm_failed: set = set()
+        # generation log-probabilities: log-probability twins of the decode buckets (lazy), keyed
+        # (bucket, "fused" | "filt" | "fsm") by the sampler they carry; _step_logprob -- the [S] f32
+        # values of the step being launched, beside its sampled ids
+        self.graphs_lp: Dict[Tuple[int, str], _DecodeGraph] = {}
+        self._lp_failed: set = set()
+        self._step_logprob: Optional[torch.Tensor] = None
         self._static = None
         self.graph_pool = None
         self.stats = {"steps": 0, "graph_steps": 0, "tokens": 0, "prefill_steps": 0, "prefill_step_tokens": 0,
                       "prefill_tile_pad_rows": 0, "prefill_m_hist": [0] * len(PREFILL_M_BUCKETS), "gpu_graph_s": 0.0, "gpu_eager_s": 0.0,
                       "gpu_idle_s": 0.0, "gpu_idle_gaps": 0, "_prev_end_ev": None, "overlap_steps": 0,
-                      "constrained_steps": 0, "constrained_tokens": 0}
+                      "constrained_steps": 0, "constrained_tokens": 0, "logprob_steps": 0}
         # TP prefill steps of >= overlap_min_rows rows run as two micro-batches whose all-reduces
         # overlap the other half's compute (PENNY_TP_OVERLAP=0 disables)
         self.tp_overlap = os.environ.get("PENNY_TP_OVERLAP", "1") == "1"
@@ -341,8 +365,10 @@ class ModelRunner:
         # a speculative chunk samples draft + 1 rows (engine.speculative: drafts <= 16 tokens)
         self.max_samplers = 17 * max(self.max_decode_batch, max_decode_batch) + 1024
         self.last_sampled = torch.zeros(self.max_samplers, dtype=torch.int32, device=self.device)
-        # one slot past the sampled ids carries the custom all-reduce's timeout flag back with them
-        self._pinned_out = ([torch.zeros(self.max_samplers + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
+        # one slot past the sampled ids carries the custom all-reduce's timeout flag back with them, and
+        # the slots from _lp_off on the step's log-probabilities (f32 bits): one buffer, one event
+        self._lp_off = self.max_samplers + 1
+        self._pinned_out = ([torch.zeros(2 * self.max_samplers + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
                             if self.on_gpu else None)
         self._out_flip = 0
         self._ev_ring: Optional[List[Tuple[torch.cuda.Event, torch.cuda.Event]]] = None
@@ -537,16 +563,30 @@ class ModelRunner:
             state = self._resolve_fsm(self._to_dev(si.fsm_state))
         h = self._hidden(si)
         hs = h.index_select(0, self._to_dev(si.logits_idx))
+        lp = si.want_logprobs
         if state is not None:              # constrained rows: logits -> masked sampler, as top-k / top-p steps
-            return self.sample(self.model.logits(hs), si, state)
+            return self._sample_logits(self.model.logits(hs), si, state)
         if not self._has_filters(si) and self._shard_sampling():
             self.stats["vocab_parallel_sample_steps"] = self.stats.get("vocab_parallel_sample_steps", 0) + 1
             return self.model.sample_vocab_parallel(hs, self._to_dev(si.temps), self._to_dev(si.seeds))
         if not self._has_filters(si) and self._fused_sampling(hs):
             self.stats["fused_lm_head_steps"] = self.stats.get("fused_lm_head_steps", 0) + 1
+            if lp:                         # the same tokens, and their log-probabilities, still without logits
+                out, self._step_logprob = ops.lm_head_sample_logprob(
+                    hs, self.model.lm_weight(), self._to_dev(si.temps), self._to_dev(si.seeds), wt=self._lm_tiled())
+                return out
             return ops.lm_head_sample(hs, self.model.lm_weight(), self._to_dev(si.temps), self._to_dev(si.seeds),
                                       wt=self._lm_tiled())
-        return self.sample(self.model.logits(hs), si)
+        return self._sample_logits(self.model.logits(hs), si)
+
+    def _sample_logits(self, logits: torch.Tensor, si: StepInputs, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``sample`` on a step that holds its logits; a step that wants log-probabilities reads them
+        off the same logits right after the (untouched) sampler."""
+        logits = logits.contiguous()
+        out = self.sample(logits, si, state)
+        if si.want_logprobs:
+            self._step_logprob = ops.token_logprobs(logits, out)
+        return out
 
     def sample(self, logits: torch.Tensor, si: StepInputs, state: Optional[torch.Tensor] = None) -> torch.Tensor:
         temps = self._to_dev(si.temps)
@@ -620,6 +660,10 @@ class ModelRunner:
                     self._staged = None
         n = len(si.logits_idx)
         self.last_sampled[:n].copy_(out[:n].to(torch.int32), non_blocking=True)
+        lpv = None
+        if si.want_logprobs:
+            lpv, self._step_logprob = self._step_logprob, None
+            self.stats["logprob_steps"] += 1
         if si.fsm_state is not None:
             so, self._step_state_out = self._step_state_out, None
             self.last_fsm_state[:n].copy_(so[:n], non_blocking=True)
@@ -628,13 +672,16 @@ class ModelRunner:
         ar = comm.custom_all_reduce()
         if not self.on_gpu:
             cpu = out[:n].clone()
+            cpu_lp = lpv[:n].float().clone() if lpv is not None else None
             if ar is not None:           # a host-side stand-in (tests): its flag is host memory
                 return PendingStep(None, n, torch.cat([cpu.to(torch.int32), ar.err.to(torch.int32)[:1]]), None,
-                                   check_err=True)
-            return PendingStep(cpu, n, None, None)
+                                   check_err=True, cpu_lp=cpu_lp)
+            return PendingStep(cpu, n, None, None, cpu_lp=cpu_lp)
         host = self._pinned_out[self._out_flip]
         self._out_flip ^= 1
         host[:n].copy_(out[:n], non_blocking=True)
+        if lpv is not None:
+            host[self._lp_off:self._lp_off + n].view(torch.float32).copy_(lpv[:n], non_blocking=True)
         if ar is not None:
             # the xGMI all-reduce never raises from the device: a peer that missed its bounded wait
             # sets ar.err and the step's sums are stale, so the flag rides the per-step host sync
@@ -642,7 +689,7 @@ class ModelRunner:
         ev = end_ev
         ev.record()
         return PendingStep(None, n, host, ev, start_ev, self.stats, "gpu_graph_s" if graph else "gpu_eager_s",
-                           check_err=ar is not None)
+                           check_err=ar is not None, lp_off=self._lp_off if lpv is not None else -1)
 
     def _forward_only(self, si: StepInputs) -> None:
         self._hidden(si)
@@ -679,6 +726,7 @@ class ModelRunner:
         self.graphs.clear()
         self.graphs_filt.clear()
         self.graphs_fsm.clear()
+        self.graphs_lp.clear()
         self.use_graphs = False
         self._dual = False
 
@@ -740,7 +788,7 @@ class ModelRunner:
                                                          self.device)
         return self._dual
 
-    def _run_static(self, B: int, filtered: bool = False, fsm: bool = False) -> torch.Tensor:
+    def _run_static(self, B: int, filtered: bool = False, fsm: bool = False, lp: bool = False) -> torch.Tensor:
         s = self._static
         self._gather_pending(s["ids"], s["src"][:B], 0)
         if fsm:      # carry codes -> states, in place, before the sampler of this graph writes state_out
@@ -759,20 +807,30 @@ class ModelRunner:
         if fsm:
             # the constrained twin: mask, then the top-k / top-p threshold (unfiltered rows leave it
             # after reading their parameters), then the sampler and the state update
+            logits = self.model.logits(h)
             out, self._step_state_out = ops.sample_constrained(
-                self.model.logits(h), s["temps"][:B], s["seeds"][:B], s["fsm"][:B], self.fsm,
+                logits, s["temps"][:B], s["seeds"][:B], s["fsm"][:B], self.fsm,
                 top_k=s["top_k"][:B], top_p=s["top_p"][:B])
+            if lp:
+                self._step_logprob = ops.token_logprobs(logits, out)
             return out
         if not filtered:
             if self._shard_sampling():     # TP: top-k / top-p rows of this bucket replay eagerly
                 return self.model.sample_vocab_parallel(h, s["temps"][:B], s["seeds"][:B])
             if self._fused_sampling(h):
+                if lp:
+                    out, self._step_logprob = ops.lm_head_sample_logprob(
+                        h, self.model.lm_weight(), s["temps"][:B], s["seeds"][:B], wt=self._lm_tiled())
+                    return out
                 return ops.lm_head_sample(h, self.model.lm_weight(), s["temps"][:B], s["seeds"][:B],
                                           wt=self._lm_tiled())
         logits = self.model.logits(h)
         # the top-k/top-p threshold kernel is always in the graph: unfiltered rows (k=0, p=1) exit
         # after reading their parameters
-        return ops.sample(logits, s["temps"][:B], s["seeds"][:B], top_k=s["top_k"][:B], top_p=s["top_p"][:B])
+        out = ops.sample(logits, s["temps"][:B], s["seeds"][:B], top_k=s["top_k"][:B], top_p=s["top_p"][:B])
+        if lp:
+            self._step_logprob = ops.token_logprobs(logits, out)
+        return out
 
     def capture_graphs(self) -> None:
         if not self.use_graphs:
@@ -800,34 +858,49 @@ class ModelRunner:
         """A decode step its bucket's graph cannot sample: top-k / top-p rows when the graph samples
         inside the LM head, or constrained rows (any graph).  At TP=1 it replays the bucket's TWIN
         (filtered: logits -> threshold -> sampler; constrained: logits -> masked threshold -> masked
-        sampler + state update), captured on the first such step; under TP it runs eagerly."""
+        sampler + state update), captured on the first such step; under TP it runs eagerly.  A step
+        that wants log-probabilities always needs a twin (``graphs_lp``): the bucket's sampler in its
+        log-probability form."""
         fsm = si.fsm_state is not None
-        if not fsm and not self._has_filters(si):
+        lp = si.want_logprobs
+        if not fsm and not lp and not self._has_filters(si):
             return False
         if not self.graphs:
             self.capture_graphs()
         B = self._bucket(si.num_decode)
         G = self.graphs.get(B)
-        if G is None or not (G.fused or fsm):
+        if G is None or not (G.fused or fsm or lp):
             return False
         if getattr(self.model, "tp_size", 1) > 1:
             return True
-        twins, failed = (self.graphs_fsm, self._fsm_failed) if fsm else (self.graphs_filt, self._filt_failed)
-        if B in failed:
+        if lp:      # a log-probability step replays the log-probability twin of the sampler it needs
+            key = (B, self._lp_kind(si, G))
+            twins, failed = self.graphs_lp, self._lp_failed
+        else:
+            key = B
+            twins, failed = (self.graphs_fsm, self._fsm_failed) if fsm else (self.graphs_filt, self._filt_failed)
+        if key in failed:
             return True
-        if B not in twins:
+        if key not in twins:
             try:
-                self._capture_twin(B, fsm)
+                self._capture_twin(B, fsm, lp=key[1] if lp else None)
             except Exception as e:  # noqa: BLE001 - e.g. out of memory after the KV pool took HBM
                 # (ADVICE r5): this bucket's filtered / constrained rows stay on the eager path for good
-                kind = "constrained" if fsm else "filtered"
+                kind = ("constrained" if fsm else "filtered") if not lp else f"log-probability ({key[1]})"
                 logger.warning(f"{kind} decode graph for batch {B} not captured ({e}); running it eagerly")
-                failed.add(B)
+                failed.add(key)
                 torch.cuda.synchronize(self.device)
                 return True
         return False
 
-    def _capture_twin(self, B: int, fsm: bool) -> None:
+    def _lp_kind(self, si: StepInputs, G: _DecodeGraph) -> str:
+        """Which sampler a log-probability step of this bucket needs: the masked one, the logits one
+        (top-k / top-p rows, or a bucket that never samples in the LM head), or the fused LM head."""
+        if si.fsm_state is not None:
+            return "fsm"
+        return "filt" if self._has_filters(si) or not G.fused else "fused"
+
+    def _capture_twin(self, B: int, fsm: bool, lp: Optional[str] = None) -> None:
         """Capture mid-serving: the static inputs still hold the step in flight, so the warm-up and
         capture passes run with every KV slot masked (< 0: no cache write), no pending-token
         gather and no automaton state -- they must not rewrite live sequences' KV -- and the inputs
@@ -837,19 +910,24 @@ class ModelRunner:
         s["slots"][:B].fill_(-1)
         s["src"][:B].fill_(-1)
         s["fsm"][:B].fill_(-1)
+        filtered = lp != "fused"                  # lp: the twin's sampler ("fused" | "filt" | "fsm"), None: no values
         try:
             for _ in range(2):
-                self._run_static(B, filtered=True, fsm=fsm)
+                self._run_static(B, filtered=filtered, fsm=fsm, lp=lp is not None)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self.graph_pool):
-                out = self._run_static(B, filtered=True, fsm=fsm)
-            if fsm:
+                out = self._run_static(B, filtered=filtered, fsm=fsm, lp=lp is not None)
+            if lp is not None:
+                self.graphs_lp[(B, lp)] = _DecodeGraph(g, B, out, lp == "fused", self._step_state_out if fsm else None,
+                                                       self._step_logprob)
+            elif fsm:
                 self.graphs_fsm[B] = _DecodeGraph(g, B, out, False, self._step_state_out)
             else:
                 self.graphs_filt[B] = _DecodeGraph(g, B, out, False)
         finally:                                  # the step in flight keeps its inputs either way
             self._step_state_out = None
+            self._step_logprob = None
             s["slots"][:B].copy_(saved[0])
             s["src"][:B].copy_(saved[1])
             s["fsm"][:B].copy_(saved[2])
@@ -867,7 +945,9 @@ class ModelRunner:
         n = si.num_decode
         B = self._bucket(n)
         G = self.graphs[B]
-        if si.fsm_state is not None:
+        if si.want_logprobs:
+            G = self.graphs_lp[(B, self._lp_kind(si, G))]
+        elif si.fsm_state is not None:
             G = self.graphs_fsm[B]
         elif G.fused and self._has_filters(si) and B in self.graphs_filt:
             G = self.graphs_filt[B]
@@ -908,4 +988,5 @@ class ModelRunner:
         G.graph.replay()
         self.stats["graph_steps"] += 1
         self._step_state_out = G.state_out
+        self._step_logprob = G.logprob
         return G.out[:n]

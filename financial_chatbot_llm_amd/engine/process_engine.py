@@ -48,6 +48,7 @@ class RemoteSeq:
     """Parent-side stand-in for the child's ``Sequence``: the tokens streamed so far."""
     output_ids: List[int] = field(default_factory=list)
     finish_reason: Optional[str] = None
+    output_logprobs: List[Optional[float]] = field(default_factory=list)   # SamplingParams.logprobs requests
 
 
 def _engine_main(cfg: EngineConfig, device_index: Optional[int], req_conn, out_conn, warmup: bool) -> None:
@@ -119,7 +120,8 @@ def _engine_main(cfg: EngineConfig, device_index: Optional[int], req_conn, out_c
             if len(step_times) > 4096:
                 del step_times[:2048]
             if outs:
-                out_conn.send(("out", [(o.request_id, o.new_token_ids, o.finished, o.finish_reason) for o in outs]))
+                out_conn.send(("out", [(o.request_id, o.new_token_ids, o.finished, o.finish_reason, o.new_logprobs)
+                                      for o in outs]))
     finally:
         if prof is not None:
             prof.disable()
@@ -196,16 +198,19 @@ class ProcessAsyncEngine:
             kind = msg[0]
             if kind == "out":
                 by_loop: Dict = {}
-                for rid, new_ids, finished, reason in msg[1]:
+                for rid, new_ids, finished, reason, new_lps in msg[1]:
                     sink = self._sinks.get(rid)
                     if sink is None:
                         continue
                     seq = self._seqs.get(rid)
                     if seq is not None:
                         seq.output_ids.extend(new_ids)
+                        if new_lps is not None:
+                            seq.output_logprobs.extend(new_lps)
                         if finished:
                             seq.finish_reason = reason
-                    by_loop.setdefault(sink[0], []).append((sink[1], StepOutput(rid, new_ids, finished, reason, seq)))
+                    by_loop.setdefault(sink[0], []).append((sink[1], StepOutput(rid, new_ids, finished, reason, seq,
+                                                                                new_lps)))
                 for loop, items in by_loop.items():
                     try:
                         loop.call_soon_threadsafe(_deliver, items)

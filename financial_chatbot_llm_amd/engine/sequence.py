@@ -42,6 +42,11 @@ class SamplingParams:
     # inside the automaton's language (the device sampler masks the rest); teacher-forced outputs
     # (forced_output) sample nothing and ignore it.  TP = 1 without CP only.
     constraint: Optional[object] = None
+    # report each sampled token's log-probability (Sequence.output_logprobs, StepOutput.new_logprobs):
+    # log softmax of the raw bf16 logits at temperature 1 -- the quantity score() reports; the
+    # temperature, top-k / top-p and the constraint choose the token, not the number.  Never changes a
+    # token.  TP = 1 without CP only.
+    logprobs: bool = False
 
 
 class SeqStatus(enum.Enum):
@@ -62,6 +67,14 @@ class Sequence:
         self.request_id = request_id
         self.prompt_ids = list(prompt_ids)
         self.output_ids: List[int] = []
+        # with params.logprobs: one entry per EMITTED output token (every token a StepOutput has
+        # handed out), so output_logprobs[i] belongs to output_ids[i] and the lists are equal in
+        # length whenever nothing is in flight (always once finished); what output_ids holds beyond
+        # -- a PENDING placeholder, a known run or a prompt-lookup draft of the step in flight -- has
+        # no entry yet, so dropping a draft (drop_draft, a rejected verification) touches nothing
+        # here.  A sampled token carries its log-probability, a token appended without a sample
+        # (forced_output, jump-forward, grammar-forced) None.
+        self.output_logprobs: List[Optional[float]] = []
         self.params = params
         self.status = SeqStatus.WAITING
         self.block_table: List[int] = []

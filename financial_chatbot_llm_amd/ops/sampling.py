@@ -167,6 +167,136 @@ def lm_head_sample(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor,
 
 
 # ----------------------------------------------------------------------------------------------
+# Generation log-probabilities: the sampled token's log softmax over the row's raw bf16-rounded
+# logits at temperature 1 (the quantity ``lm_head_logprobs`` scores prompts with), whatever the
+# temperature, filters or automaton mask that chose it.  The fused LM heads have a log-probability
+# form each (``gemm_prefill.hip`` EPI_SAMPLE_LP, ``gemm_splitk.hip`` SK_SAMPLE_LP): the same pick bit
+# for bit, plus per partial the chosen logit and a (max, sum exp) pair, merged by
+# lm_sample_logprob_final_kernel.  Steps that hold logits call ``token_logprobs`` after their sampler.
+# ----------------------------------------------------------------------------------------------
+# Row ranges (inclusive) where the microbenchmark has logits GEMM + sample + token_logprobs ahead of
+# the fused log-probability form (bench/kernels.py lm_head_sample_logprob_sweep,
+# profiles/lm_head_sample_logprob_sweep.jsonl: by 10-45 us; the plain fused sampler trails the
+# unfused path in the same ranges).  Taken only with PENNY_LOGPROB_UNFUSED=1: the library GEMM rounds
+# logits in another order than the fused kernels, so on that route a token can differ from the one
+# the same request samples with log-probabilities off (up to logit rounding, as ``lm_head_sample``
+# documents for fused vs unfused) -- by default the fused form keeps every token.
+LOGPROB_UNFUSED_ROWS = ((1, 32), (96, 128))
+
+
+def _logprob_unfused(M: int) -> bool:
+    import os
+    return os.environ.get("PENNY_LOGPROB_UNFUSED", "0") == "1" and any(a <= M <= b for a, b in LOGPROB_UNFUSED_ROWS)
+
+
+def _token_logprobs_ref(logits: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    lf = logits.float()
+    V = lf.shape[1]
+    idl = ids.to(device=lf.device, dtype=torch.long)
+    inside = (idl >= 0) & (idl < V)
+    lp = torch.log_softmax(lf, -1).gather(1, idl.clamp(0, V - 1)[:, None])[:, 0]
+    return torch.where(inside, lp, torch.full_like(lp, float("nan")))
+
+
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """log softmax(logits)[ids] per row: logits [B, V] bf16 or f32, ids [B] integer token ids -> f32 [B],
+    over the raw logits at temperature 1.  A row holding a NaN logit, or an id outside [0, V), gives
+    NaN.  One HIP pass per row on the device (``penny_token_logprob``), f32 log-softmax on the CPU."""
+    B, V = logits.shape
+    if not N.use_native(logits):
+        lp = _token_logprobs_ref(logits, ids)
+        if out is not None:
+            out.copy_(lp)
+            return out
+        return lp
+    out = torch.empty((B,), dtype=torch.float32, device=logits.device) if out is None else out
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"token_logprobs takes bf16 or f32 logits, not {logits.dtype}")
+    logits = _aligned_rows(logits)
+    idc = ids.to(device=logits.device, dtype=torch.int32).contiguous()     # alive across the launch
+    N.call("penny_token_logprob", N.ptr(logits), int(logits.dtype == torch.float32), logits.stride(0), N.ptr(idc),
+           N.ptr(out), B, V, N.stream())
+    return out
+
+
+def lm_head_stream_sample_logprob(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
+                                  vvalid: Optional[int] = None, voff: int = 0, out: Optional[torch.Tensor] = None,
+                                  logprob: Optional[torch.Tensor] = None, nf: Optional[int] = None,
+                                  rowmajor: Optional[bool] = None,
+                                  ring2: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`lm_head_stream_sample` (same arguments, same tokens) that also returns each token's
+    log-probability: (ids int32 [M], logprob f32 [M])."""
+    M, K = h.shape
+    Vpad = w.shape[0] * (16 if w.dim() == 4 else 1)
+    vvalid = Vpad if vvalid is None else vvalid
+    d_nf, d_r2 = stream_cfg(M)
+    nf = d_nf if nf is None else nf
+    rowmajor = (w.dim() == 2) if rowmajor is None else rowmajor
+    ring2 = d_r2 if ring2 is None else ring2
+    P = Vpad // (16 * nf) * 2
+    ws = torch.empty((5 * M * P,), dtype=torch.float32, device=h.device)
+    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
+    out = torch.empty((M,), dtype=torch.int32, device=h.device) if out is None else out
+    logprob = torch.empty((M,), dtype=torch.float32, device=h.device) if logprob is None else logprob
+    N.call("penny_lm_head_stream_sample_logprob", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, int(vvalid), int(voff),
+           N.ptr(temps), N.ptr(sd), N.ptr(ws), N.ptr(out), N.ptr(logprob), int(nf), int(rowmajor), int(ring2),
+           N.stream())
+    return out, logprob
+
+
+def lm_head_sample_logprob(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
+                           out: Optional[torch.Tensor] = None, wt: Optional[torch.Tensor] = None,
+                           vvalid: Optional[int] = None, voff: int = 0,
+                           logprob: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`lm_head_sample` that also reports how likely each sampled token was: (ids int32 [M],
+    logprob f32 [M]) with logprob = log softmax(l)[id] over the row's raw bf16-rounded logits l at
+    temperature 1 (natural log) -- the temperature chooses the token, not the number.  The tokens are
+    the ones :func:`lm_head_sample` returns for the same inputs, and the routing is the same (the
+    streaming kernel below 128 rows, the tile kernel from 128, ``PENNY_FUSED_LM_HEAD=force``).
+    ``w`` [Vpad, K] may be a padded vocabulary shard: global rows voff .. voff+vvalid-1, then padding
+    that takes no part; ids are global.  ``PENNY_LOGPROB_UNFUSED=1`` sends the row counts of
+    ``LOGPROB_UNFUSED_ROWS`` through logits + sampler + :func:`token_logprobs` instead (faster there,
+    tokens then reproducible only up to logit rounding)."""
+    import os
+    M, K = h.shape
+    Vpad = w.shape[0]
+    vvalid = Vpad if vvalid is None else int(vvalid)
+    if not 0 < vvalid <= Vpad or voff < 0:
+        raise ValueError(f"vocab shard [{voff}, {voff}+{vvalid}) does not fit {Vpad} weight rows")
+    if not N.use_native(h):
+        import torch.nn.functional as F
+        logits = F.linear(h.float(), w[:vvalid].float()).to(h.dtype)
+        ids = sample(logits, temperatures, seeds)
+        lp = _token_logprobs_ref(logits, ids)
+        ids = (ids + int(voff)).to(torch.int32)
+        if out is not None:
+            out.copy_(ids)
+            ids = out
+        if logprob is not None:
+            logprob.copy_(lp)
+            lp = logprob
+        return ids, lp
+    if _logprob_unfused(M) and os.environ.get("PENNY_FUSED_LM_HEAD") != "force":
+        from .gemm import linear
+        logits = linear(h, w[:vvalid])
+        ids = sample(logits, temperatures, seeds, out=out)
+        lp = token_logprobs(logits, ids, out=logprob)
+        if voff:
+            ids.add_(int(voff))
+        return ids, lp
+    if _stream_ok(M) and os.environ.get("PENNY_FUSED_LM_HEAD") != "force" and Vpad % (16 * stream_cfg(M)[0]) == 0:
+        return lm_head_stream_sample_logprob(h, wt if wt is not None else w, temperatures, seeds, vvalid=vvalid,
+                                             voff=voff, out=out, logprob=logprob)
+    out = torch.empty((M,), dtype=torch.int32, device=h.device) if out is None else out
+    logprob = torch.empty((M,), dtype=torch.float32, device=h.device) if logprob is None else logprob
+    ws = torch.empty((5 * M * 2 * (Vpad // 256),), dtype=torch.float32, device=h.device)
+    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
+    N.call("penny_lm_head_sample_logprob", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, vvalid, int(voff),
+           N.ptr(temps), N.ptr(sd), N.ptr(ws), N.ptr(out), N.ptr(logprob), N.stream())
+    return out, logprob
+
+
+# ----------------------------------------------------------------------------------------------
 # Vocabulary-parallel sampling (SURVEY C2 "per-rank top-k then gather"): under TP each rank scores
 # its own vocab shard -- Gumbel noise keyed by the GLOBAL token id -- and keeps one (score, id)
 # candidate per row; the candidates ([B, 2] int32 per rank) are all-gathered and the best taken.

@@ -38,7 +38,9 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
                          extra_tools=[make_plot_tool()], temperature=serving.temperature,
                          max_response_tokens=serving.max_response_tokens,
                          max_decide_tokens=serving.max_decide_tokens, max_tool_steps=max_tool_steps,
-                         today_fn=today_fn, max_transaction_tokens=retrieval_limit_tokens())
+                         today_fn=today_fn, max_transaction_tokens=retrieval_limit_tokens(),
+                         decide_logprobs=serving.decide_logprobs,
+                         decide_confidence_threshold=serving.decide_confidence_threshold)
     return Services(db=db, kafka=kafka, agent=agent, retrieval=retrieval, serving=serving)
 
 
@@ -69,7 +71,9 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
         agent = LLMAgent(llm, make_retrieval_tool(retrieval), extra_tools=[make_plot_tool()],
                          temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
                          max_decide_tokens=serving.max_decide_tokens, max_tool_steps=max_tool_steps,
-                         max_transaction_tokens=retrieval_cfg.max_limit_tokens)
+                         max_transaction_tokens=retrieval_cfg.max_limit_tokens,
+                         decide_logprobs=serving.decide_logprobs,
+                         decide_confidence_threshold=serving.decide_confidence_threshold)
     return Services(db=db or Database(), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)
 

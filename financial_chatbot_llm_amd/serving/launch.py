@@ -44,6 +44,9 @@ def parse(argv=None):
     ap.add_argument("--tool-steps", type=int, default=1, help=">1 enables the multi-step agent (retrieval + plot)")
     ap.add_argument("--no-tools", action="store_true",
                     help="legacy single-chain chat (llm_service.py): no decide step, no retrieval")
+    ap.add_argument("--decide-logprobs", action="store_true",
+                    default=os.environ.get("PENNY_DECIDE_LOGPROBS", "0").lower() in ("1", "true", "yes"),
+                    help="record the decide call's confidence, exp(mean token log-probability), in the metrics")
     ap.add_argument("--constrain-toolcalls", action="store_true",
                     default=os.environ.get("PENNY_CONSTRAIN_TOOLCALLS", "0").lower() in ("1", "true", "yes"),
                     help="decide calls sample under the tool-call token automaton (TP = 1 only)")
@@ -88,7 +91,9 @@ def build_leader_services(args, engine, device):
         agent = LLMAgent(llm, make_retrieval_tool(retrieval), extra_tools=[make_plot_tool()],
                          temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
                          max_decide_tokens=serving.max_decide_tokens, max_tool_steps=args.tool_steps,
-                         max_transaction_tokens=retrieval_limit_tokens())     # PENNY_MAX_TRANSACTION_TOKENS
+                         max_transaction_tokens=retrieval_limit_tokens(),     # PENNY_MAX_TRANSACTION_TOKENS
+                         decide_logprobs=args.decide_logprobs or serving.decide_logprobs,
+                         decide_confidence_threshold=serving.decide_confidence_threshold)
     broker = InMemoryBroker() if args.smoke else None
     return Services(db=Database(uri="" if args.smoke else None), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)
