@@ -1201,6 +1201,23 @@ PENNY_API int penny_lm_sample_final(const float* pv, const int* pi, int P, int M
   return (int)hipGetLastError();
 }
 
+// The EPI_SAMPLE tile GEMM over W [Vpad, K] (global vocabulary rows voff .. voff + vvalid - 1, then
+// padding) and the merge of its partials, to out [M] and / or pairs [M, 2]; the callers check the contract.
+// workspace: M * 2 * (Vpad / 256) floats, then as many ints.
+static int lm_head_sample_tiles(const void* X, int ldx, const void* W, int K, int M, int Vpad, int vvalid, int voff,
+                                const float* temps, const unsigned long long* seeds, void* workspace, int* out,
+                                int* pairs, hipStream_t stream) {
+  const int P = 2 * (Vpad / TN);
+  float* pv = static_cast<float*>(workspace);
+  int* pi = reinterpret_cast<int*>(pv + (long)M * P);
+  const SampleArgs sa{temps, seeds, pv, pi, voff, vvalid};
+  hipLaunchKernelGGL((gemm_prefill_kernel<EPI_SAMPLE>), grid_for(M, Vpad, 1), dim3(512), 0, stream, X, ldx, W, K,
+                     nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{},
+                     LogprobArgs{});
+  hipLaunchKernelGGL(lm_sample_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, P, out, pairs);
+  return (int)hipGetLastError();
+}
+
 // LM head + sampler fused (K11 + K12): out[m] = Gumbel-max / argmax sample of row m of
 // X [M, K] bf16 x W [V, K]^T, temps [M] f32 (<= 0: greedy), seeds [M] u64 -- the [M, V] logits are
 // never written.  workspace: M * 2 * (V / 256) floats, then as many ints.
@@ -1209,15 +1226,7 @@ PENNY_API int penny_lm_head_sample(const void* X, int ldx, const void* W, int K,
                                    const unsigned long long* seeds, void* workspace, int* out, hipStream_t stream) {
   if (M <= 0) return 0;
   if (V % TN || K % BK || ldx % 8 || !temps || !seeds || !workspace || !out) return (int)hipErrorInvalidValue;
-  const int P = 2 * (V / TN);
-  float* pv = static_cast<float*>(workspace);
-  int* pi = reinterpret_cast<int*>(pv + (long)M * P);
-  const SampleArgs sa{temps, seeds, pv, pi, 0, V};
-  hipLaunchKernelGGL((gemm_prefill_kernel<EPI_SAMPLE>), grid_for(M, V, 1), dim3(512), 0, stream, X, ldx, W, K,
-                     nullptr, 0, (const bf16*)nullptr, 0, M, V, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{},
-                     LogprobArgs{});
-  hipLaunchKernelGGL(lm_sample_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, P, out, (int*)nullptr);
-  return (int)hipGetLastError();
+  return lm_head_sample_tiles(X, ldx, W, K, M, V, V, 0, temps, seeds, workspace, out, nullptr, stream);
 }
 
 // Vocabulary-parallel form (a TP rank's LM-head shard, SURVEY C2 "per-rank top-k then gather"):
@@ -1232,15 +1241,7 @@ PENNY_API int penny_lm_head_sample_shard(const void* X, int ldx, const void* W, 
   if (Vpad % TN || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % BK || ldx % 8 || !temps || !seeds ||
       !workspace || !pairs)
     return (int)hipErrorInvalidValue;
-  const int P = 2 * (Vpad / TN);
-  float* pv = static_cast<float*>(workspace);
-  int* pi = reinterpret_cast<int*>(pv + (long)M * P);
-  const SampleArgs sa{temps, seeds, pv, pi, voff, vvalid};
-  hipLaunchKernelGGL((gemm_prefill_kernel<EPI_SAMPLE>), grid_for(M, Vpad, 1), dim3(512), 0, stream, X, ldx, W, K,
-                     nullptr, 0, (const bf16*)nullptr, 0, M, Vpad, 1, RopeArgs{}, MoeArgs{}, sa, TailArgs{},
-                     LogprobArgs{});
-  hipLaunchKernelGGL(lm_sample_final_kernel, dim3(M), dim3(256), 0, stream, pv, pi, P, (int*)nullptr, pairs);
-  return (int)hipGetLastError();
+  return lm_head_sample_tiles(X, ldx, W, K, M, Vpad, vvalid, voff, temps, seeds, workspace, nullptr, pairs, stream);
 }
 
 // Reduce a row's partials of the fused LM-head log-likelihood (EPI_LOGPROB) to stats[row] =

@@ -440,9 +440,16 @@ constexpr bool pair_fits() {
   return Ring<NF, MT, RKB, MAXB, 2>::NBUF >= 3;
 }
 
+// The wave split: a workgroup's 4 waves tile its (16*nf W rows) x (16*mt tokens) as WA x 4/WA, and this
+// returns WA -- picked per shape to minimise fragment reads per wave (NF/WA + MT/WB), (NF + MT) even.
+// mt: token tiles, 1 .. 16; the instantiated sizes {2, 4, 6, 8, 12, 16} and every count that rounds up
+// to one of them give the same answer, so the launchers' template arguments and a host-side partial
+// count (the streaming LM head's pstride) cannot disagree.
+constexpr int wave_split(int nf, int mt) { return nf >= 6 || mt <= 2 || (mt > 4 && mt <= 6) ? 2 : 1; }
+
 // one launch of splitk_gemm_kernel<NF, MT, WA, EPI, *, 150, MAXB, *> with the W layout / stage pairing
 // of wrow (runtime) mapped onto the template arguments
-template <int NF, int MT, int WA, int EPI, int MAXB, class... A>
+template <int NF, int MT, int EPI, int MAXB, int WA = wave_split(NF, MT), class... A>
 int launch_any(int wrow, bool pair_ok, dim3 grid, hipStream_t st, A... args) {
   const bool rm = wrow & 1;
   if constexpr (pair_fits<NF, MT, 150, MAXB>()) {
@@ -457,32 +464,36 @@ int launch_any(int wrow, bool pair_ok, dim3 grid, hipStream_t st, A... args) {
   return (int)hipGetLastError();
 }
 
-template <int NF, int MT, int WA>
+template <int NF, int MT>
 int launch(const void* X, int ldx, const void* Wt, int K, float* P, int M, int N, int S, int wrow, hipStream_t st) {
-  return launch_any<NF, MT, WA, SK_SLAB, 8>(wrow, (K / S) % 128 == 0, dim3((N / (16 * NF)) * S, (M + 16 * MT - 1) / (16 * MT)), st, (const bf16*)X,
+  return launch_any<NF, MT, SK_SLAB, 8>(wrow, (K / S) % 128 == 0, dim3((N / (16 * NF)) * S, (M + 16 * MT - 1) / (16 * MT)), st, (const bf16*)X,
                                             ldx, (const bf16*)Wt, K, P, M, N, S, (bf16*)nullptr, 0, SkSample{});
 }
 
-template <int NF, int MT, int WA>
+// NF = 2 is one (gate, up) row-group pair per workgroup, which one wave must hold whole: WA = 1 there
+// (4 token-tile wave columns, so MT a multiple of 4), whatever wave_split says
+template <int NF, int MT>
 int launch_silu(const void* X, int ldx, const void* Wt, int K, void* Y, int ldy, int M, int N, int wrow,
                 hipStream_t st) {
-  return launch_any<NF, MT, WA, SK_SILU, NF == 2 ? 16 : 8>(wrow, K % 128 == 0, dim3(N / (16 * NF), (M + 16 * MT - 1) / (16 * MT)), st, (const bf16*)X,
+  constexpr int WA = NF == 2 ? 1 : wave_split(NF, MT);
+  return launch_any<NF, MT, SK_SILU, NF == 2 ? 16 : 8, WA>(wrow, K % 128 == 0, dim3(N / (16 * NF), (M + 16 * MT - 1) / (16 * MT)), st, (const bf16*)X,
                                                           ldx, (const bf16*)Wt, K, (float*)nullptr, M, N, 1, (bf16*)Y,
                                                           ldy, SkSample{});
 }
 
-template <int NF, int MT, int WA>
+template <int NF, int MT>
 int launch_bf16(const void* X, int ldx, const void* Wt, int K, void* Y, int ldy, int M, int N, int wrow,
                 hipStream_t st) {
-  return launch_any<NF, MT, WA, SK_BF16, 16>(wrow, K % 128 == 0, dim3(N / (16 * NF), (M + 16 * MT - 1) / (16 * MT)), st, (const bf16*)X, ldx,
+  return launch_any<NF, MT, SK_BF16, 16>(wrow, K % 128 == 0, dim3(N / (16 * NF), (M + 16 * MT - 1) / (16 * MT)), st, (const bf16*)X, ldx,
                                              (const bf16*)Wt, K, (float*)nullptr, M, N, 1, (bf16*)Y, ldy, SkSample{});
 }
 
 // the streaming LM head: row-major W (wrow) or its fragment-tiled copy; ring budget 150 KiB (one
 // workgroup per CU) or 72 KiB (two)
-template <int NF, int MT, int WA, int EPI = SK_SAMPLE>
+template <int NF, int MT, int EPI>
 int launch_sample(const void* X, int ldx, const void* Wt, int K, int M, int N, int wrow, int ring2, const SkSample& sa,
                   hipStream_t st) {
+  constexpr int WA = wave_split(NF, MT);
   const dim3 grid(N / (16 * NF)), block(256);
 #define SK_SAMPLE_LAUNCH(WROW_, KB_)                                                                               \
   hipLaunchKernelGGL((splitk_gemm_kernel<NF, MT, WA, EPI, WROW_, KB_, 16>), grid, block, 0, st, (const bf16*)X, ldx, \
@@ -520,23 +531,18 @@ PENNY_API int penny_gateup_silu_gemm(const void* X, int ldx, const void* Wt, int
   const int mt = min((M + 15) / 16, 16);   // > 256 rows: 256-row token chunks on grid y
   // nf = 2 (one (gate, up) pair per workgroup, WA = 1): twice the workgroups of nf = 4 for narrow
   // TP shards (Llama-3-70B TP=8 gate|up: N = 7168 -> 224 workgroups)
-  if (nf == 2) {   // WA = 1 -> 4 token-tile wave columns: token tiles rounded up to a multiple of 4
-    if (mt <= 4) return launch_silu<2, 4, 1>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
-    if (mt <= 8) return launch_silu<2, 8, 1>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
-    if (mt <= 12) return launch_silu<2, 12, 1>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
-    return launch_silu<2, 16, 1>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
+  if (nf == 2) {   // launch_silu's WA = 1: token tiles rounded up to a multiple of 4
+    if (mt <= 4) return launch_silu<2, 4>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
+    if (mt <= 8) return launch_silu<2, 8>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
+    if (mt <= 12) return launch_silu<2, 12>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
+    return launch_silu<2, 16>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);
   }
-#define GU_CASE(MT_, WA4_, WA8_)                                                          \
-  if (mt <= MT_) {                                                                      \
-    if (nf == 4) return launch_silu<4, MT_, WA4_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream); \
-    return launch_silu<8, MT_, WA8_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);              \
+#define GU_CASE(MT_)                                                                 \
+  if (mt <= MT_) {                                                                   \
+    if (nf == 4) return launch_silu<4, MT_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream); \
+    return launch_silu<8, MT_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);              \
   }
-  GU_CASE(2, 2, 2)
-  GU_CASE(4, 1, 2)
-  GU_CASE(6, 2, 2)
-  GU_CASE(8, 1, 2)
-  GU_CASE(12, 1, 2)
-  GU_CASE(16, 1, 2)
+  GU_CASE(2) GU_CASE(4) GU_CASE(6) GU_CASE(8) GU_CASE(12) GU_CASE(16)
 #undef GU_CASE
   return (int)hipErrorInvalidValue;
 }
@@ -554,20 +560,14 @@ PENNY_API int penny_splitk_gemm(const void* X, int ldx, const void* Wt, int K, v
     return (int)hipErrorInvalidValue;
   const int mt = min((M + 15) / 16, 16);   // > 256 rows: 256-row token chunks on grid y
   float* p = static_cast<float*>(P);
-#define SK_CASE(MT_, WA2_, WA4_, WA8_)                                                 \
-  if (mt <= MT_) {                                                                     \
-    if (nf == 2) return launch<2, MT_, WA2_>(X, ldx, Wt, K, p, M, N, S, wrow, stream); \
-    if (nf == 4) return launch<4, MT_, WA4_>(X, ldx, Wt, K, p, M, N, S, wrow, stream); \
-    if (nf == 6) return launch<6, MT_, 2>(X, ldx, Wt, K, p, M, N, S, wrow, stream);    \
-    return launch<8, MT_, WA8_>(X, ldx, Wt, K, p, M, N, S, wrow, stream);              \
+#define SK_CASE(MT_)                                                             \
+  if (mt <= MT_) {                                                               \
+    if (nf == 2) return launch<2, MT_>(X, ldx, Wt, K, p, M, N, S, wrow, stream); \
+    if (nf == 4) return launch<4, MT_>(X, ldx, Wt, K, p, M, N, S, wrow, stream); \
+    if (nf == 6) return launch<6, MT_>(X, ldx, Wt, K, p, M, N, S, wrow, stream); \
+    return launch<8, MT_>(X, ldx, Wt, K, p, M, N, S, wrow, stream);              \
   }
-  // (NF + MT) even; wave split picked to minimise fragment reads per wave (NF/WA + MT/WB)
-  SK_CASE(2, 2, 2, 2)
-  SK_CASE(4, 1, 1, 2)
-  SK_CASE(6, 2, 2, 2)
-  SK_CASE(8, 1, 1, 2)
-  SK_CASE(12, 1, 1, 2)
-  SK_CASE(16, 1, 1, 2)
+  SK_CASE(2) SK_CASE(4) SK_CASE(6) SK_CASE(8) SK_CASE(12) SK_CASE(16)
 #undef SK_CASE
   return (int)hipErrorInvalidValue;
 }
@@ -635,20 +635,49 @@ PENNY_API int penny_splitk_gemm_bf16(const void* X, int ldx, const void* Wt, int
   if (M > (1 << 20) || K % 64 || ldx % 8 || ldy % 4 || (nf != 2 && nf != 4 && nf != 8) || N % (16 * nf))
     return (int)hipErrorInvalidValue;
   const int mt = min((M + 15) / 16, 16);   // > 256 rows: 256-row token chunks on grid y
-#define BF_CASE(MT_, WA2_, WA4_, WA8_)                                                          \
-  if (mt <= MT_) {                                                                            \
-    if (nf == 2) return launch_bf16<2, MT_, WA2_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);  \
-    if (nf == 4) return launch_bf16<4, MT_, WA4_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);  \
-    return launch_bf16<8, MT_, WA8_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);               \
+#define BF_CASE(MT_)                                                                    \
+  if (mt <= MT_) {                                                                      \
+    if (nf == 2) return launch_bf16<2, MT_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream); \
+    if (nf == 4) return launch_bf16<4, MT_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream); \
+    return launch_bf16<8, MT_>(X, ldx, Wt, K, Y, ldy, M, N, wrow, stream);              \
   }
-  BF_CASE(2, 2, 2, 2)
-  BF_CASE(4, 1, 1, 2)
-  BF_CASE(6, 2, 2, 2)
-  BF_CASE(8, 1, 1, 2)
-  BF_CASE(12, 1, 1, 2)
-  BF_CASE(16, 1, 1, 2)
+  BF_CASE(2) BF_CASE(4) BF_CASE(6) BF_CASE(8) BF_CASE(12) BF_CASE(16)
 #undef BF_CASE
   return (int)hipErrorInvalidValue;
+}
+
+// lm_sample_logprob_final_kernel's launcher (gemm_prefill.hip)
+extern "C" int penny_lm_sample_logprob_final(const float* pv, const int* pi, const float* pl, const float* pm,
+                                             const float* ps, int P, int M, int* out, float* logprob,
+                                             hipStream_t stream);
+
+// What the two streaming LM heads share: the shape contract, the (score, token) partial planes pv / pi
+// [M, pstride] at the head of the workspace, and the GEMM + sampler launch with epilogue EPI; then
+// merge(pv, pi, pstride) reduces the partials.  pstride counts one partial per (workgroup tile, wave
+// row), so it is sized by the wave split the launch instantiates.
+template <int EPI, class Merge>
+static int stream_sample(const void* X, int ldx, const void* W, int K, int M, int Vpad, int vvalid, int voff,
+                         const float* temps, const unsigned long long* seeds, void* workspace, int nf, int wrow,
+                         int ring2, hipStream_t stream, Merge merge) {
+  if (M > 128 || (nf != 4 && nf != 8) || Vpad % (16 * nf) || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % 64 ||
+      ldx % 8 || !temps || !seeds || !workspace)
+    return (int)hipErrorInvalidValue;
+  const int tiles = Vpad / (16 * nf), mt = (M + 15) / 16;
+  const int pstride = tiles * wave_split(nf, mt);
+  float* pv = static_cast<float*>(workspace);
+  int* pi = reinterpret_cast<int*>(pv + (long)M * pstride);
+  const SkSample sa{temps, seeds, pv, pi, pstride, voff, vvalid};
+  int rc;
+#define LS_CASE(MT_)                                                                            \
+  if (mt <= MT_) {                                                                              \
+    if (nf == 4) rc = launch_sample<4, MT_, EPI>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream); \
+    else rc = launch_sample<8, MT_, EPI>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream);         \
+  } else
+  LS_CASE(2) LS_CASE(4) LS_CASE(6) LS_CASE(8)
+  return (int)hipErrorInvalidValue;
+#undef LS_CASE
+  if (rc) return rc;
+  return merge(pv, pi, pstride);
 }
 
 // Weight-streaming LM head + sampler (K11 + K12) for decode batches, full vocabulary or a TP rank's
@@ -663,36 +692,12 @@ PENNY_API int penny_lm_head_stream_sample(const void* X, int ldx, const void* W,
                                           void* workspace, int* out, int* pairs, int nf, int wrow, int ring2,
                                           hipStream_t stream) {
   if (M <= 0) return 0;
-  if (M > 128 || (nf != 4 && nf != 8) || Vpad % (16 * nf) || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % 64 ||
-      ldx % 8 || !temps || !seeds || !workspace || (!out && !pairs))
-    return (int)hipErrorInvalidValue;
-  const int tiles = Vpad / (16 * nf), mt = (M + 15) / 16;
-  // wave split per (nf, token tiles): as penny_splitk_gemm's table
-  const int wa = nf == 8 ? 2 : (mt <= 2 || (mt > 4 && mt <= 6) ? 2 : 1);
-  const int pstride = tiles * wa;
-  float* pv = static_cast<float*>(workspace);
-  int* pi = reinterpret_cast<int*>(pv + (long)M * pstride);
-  const SkSample sa{temps, seeds, pv, pi, pstride, voff, vvalid};
-  int rc;
-#define LS_CASE(MT_, WA4_)                                                                                      \
-  if (mt <= MT_) {                                                                                              \
-    if (nf == 4) rc = launch_sample<4, MT_, WA4_>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream);              \
-    else rc = launch_sample<8, MT_, 2>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream);                          \
-  } else
-  LS_CASE(2, 2)
-  LS_CASE(4, 1)
-  LS_CASE(6, 2)
-  LS_CASE(8, 1)
-  return (int)hipErrorInvalidValue;
-#undef LS_CASE
-  if (rc) return rc;
-  return penny_lm_sample_final(pv, pi, pstride, M, out, pairs, stream);
+  if (!out && !pairs) return (int)hipErrorInvalidValue;
+  return stream_sample<SK_SAMPLE>(X, ldx, W, K, M, Vpad, vvalid, voff, temps, seeds, workspace, nf, wrow, ring2,
+                                  stream, [=](const float* pv, const int* pi, int P) {
+                                    return penny_lm_sample_final(pv, pi, P, M, out, pairs, stream);
+                                  });
 }
-
-// lm_sample_logprob_final_kernel's launcher (gemm_prefill.hip)
-extern "C" int penny_lm_sample_logprob_final(const float* pv, const int* pi, const float* pl, const float* pm,
-                                             const float* ps, int P, int M, int* out, float* logprob,
-                                             hipStream_t stream);
 
 // penny_lm_head_stream_sample with the sampled token's log-probability: out [M] int32 = the token the
 // plain kernel samples (bit for bit), logprob [M] f32 = log softmax of the row's raw bf16-rounded
@@ -703,29 +708,12 @@ PENNY_API int penny_lm_head_stream_sample_logprob(const void* X, int ldx, const 
                                                   const unsigned long long* seeds, void* workspace, int* out,
                                                   float* logprob, int nf, int wrow, int ring2, hipStream_t stream) {
   if (M <= 0) return 0;
-  if (M > 128 || (nf != 4 && nf != 8) || Vpad % (16 * nf) || vvalid <= 0 || vvalid > Vpad || voff < 0 || K % 64 ||
-      ldx % 8 || !temps || !seeds || !workspace || !out || !logprob)
-    return (int)hipErrorInvalidValue;
-  const int tiles = Vpad / (16 * nf), mt = (M + 15) / 16;
-  const int wa = nf == 8 ? 2 : (mt <= 2 || (mt > 4 && mt <= 6) ? 2 : 1);
-  const int pstride = tiles * wa;
-  const long plane = (long)M * pstride;
-  float* pv = static_cast<float*>(workspace);
-  int* pi = reinterpret_cast<int*>(pv + plane);
-  const SkSample sa{temps, seeds, pv, pi, pstride, voff, vvalid};
-  int rc;
-#define LS_CASE(MT_, WA4_)                                                                                      \
-  if (mt <= MT_) {                                                                                              \
-    if (nf == 4) rc = launch_sample<4, MT_, WA4_, SK_SAMPLE_LP>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream); \
-    else rc = launch_sample<8, MT_, 2, SK_SAMPLE_LP>(X, ldx, W, K, M, Vpad, wrow, ring2, sa, stream);            \
-  } else
-  LS_CASE(2, 2)
-  LS_CASE(4, 1)
-  LS_CASE(6, 2)
-  LS_CASE(8, 1)
-  return (int)hipErrorInvalidValue;
-#undef LS_CASE
-  if (rc) return rc;
-  return penny_lm_sample_logprob_final(pv, pi, pv + 2 * plane, pv + 3 * plane, pv + 4 * plane, pstride, M, out,
-                                       logprob, stream);
+  if (!out || !logprob) return (int)hipErrorInvalidValue;
+  return stream_sample<SK_SAMPLE_LP>(X, ldx, W, K, M, Vpad, vvalid, voff, temps, seeds, workspace, nf, wrow, ring2,
+                                     stream, [=](const float* pv, const int* pi, int P) {
+                                       const long plane = (long)M * P;   // the LP epilogue's planes 2..4
+                                       return penny_lm_sample_logprob_final(pv, pi, pv + 2 * plane, pv + 3 * plane,
+                                                                            pv + 4 * plane, P, M, out, logprob,
+                                                                            stream);
+                                     });
 }

@@ -15,7 +15,7 @@ import itertools
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -294,6 +294,14 @@ class PendingStep:
         return self._host[:self.n].tolist()
 
 
+class Sampled(NamedTuple):
+    """What the sampling stage leaves on the device: the token per row, the next automaton states
+    (sampler "fsm" only) and the tokens' log-probabilities (only when asked for)."""
+    out: torch.Tensor
+    state_out: Optional[torch.Tensor] = None
+    logprob: Optional[torch.Tensor] = None
+
+
 class _DecodeGraph:
     def __init__(self, graph, B: int, out: torch.Tensor, fused: bool = False,
                  state_out: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None):
@@ -302,6 +310,41 @@ class _DecodeGraph:
         # logprob: a log-probability twin's [B] f32 values (beside ``out``)
         self.graph, self.B, self.out, self.fused, self.state_out = graph, B, out, fused, state_out
         self.logprob = logprob
+
+
+# Which sampler a step runs, and which captured graph holds it, decided from booleans alone.  Samplers:
+# "fsm" logits -> masked threshold -> masked sampler + automaton state update, "shard" the TP
+# vocabulary-parallel sampler, "fused" inside the LM head (no logits, no top-k / top-p), "logits"
+# logits -> threshold -> sampler.
+def sampler_kind(fsm: bool, filters: bool, shard: bool, fused: bool) -> str:
+    """Sampler of an eager step: constrained rows, else the shard / fused LM-head sampler where the
+    model has one and no row carries top-k / top-p, else the logits sampler."""
+    if fsm:
+        return "fsm"
+    if not filters and (shard or fused):
+        return "shard" if shard else "fused"
+    return "logits"
+
+
+def default_graph_kind(shard: bool, fused: bool) -> str:
+    """Sampler of a bucket's up-front graph; "shard" and "fused" make it a fused graph
+    (``_DecodeGraph.fused``), "logits" has the threshold kernel in the graph for every row."""
+    return "shard" if shard else "fused" if fused else "logits"
+
+
+DEFAULT_GRAPH, EAGER = "default", "eager"
+
+
+def graph_plan(fsm: bool, filters: bool, lp: bool, bucket_fused: bool, tp: bool):
+    """What runs a pure-decode step whose bucket's default graph is ``bucket_fused`` or not:
+    DEFAULT_GRAPH, EAGER, or the (sampler, lp) of the bucket's twin graph, captured on the first step
+    that needs it.  The default graph has no automaton, no log-probabilities and, when fused, no
+    top-k / top-p; twins exist at TP = 1 only."""
+    if not (fsm or lp or (filters and bucket_fused)):
+        return DEFAULT_GRAPH
+    if tp:
+        return EAGER
+    return ("fsm" if fsm else "logits" if filters or not bucket_fused else "fused"), lp
 
 
 class ModelRunner:
@@ -328,9 +371,11 @@ class ModelRunner:
         self.dual_min_batch = int(os.environ.get("PENNY_TP_DUAL_MIN_BATCH", "2"))
         self._max_decode_ws = max(max_decode_batch, 1)
         self.decode_ws2 = None
-        self.graphs: Dict[int, _DecodeGraph] = {}
-        self.graphs_filt: Dict[int, _DecodeGraph] = {}   # top-k / top-p twins of fused buckets (lazy)
-        self._filt_failed: set = set()                    # buckets whose filtered twin could not be captured
+        self.graphs: Dict[int, _DecodeGraph] = {}         # the default graph of every bucket, captured up front
+        # twins of the buckets, captured by the first step that needs one (graph_plan): keyed (bucket,
+        # sampler, log-probabilities); a key that could not be captured runs eagerly from then on
+        self.twins: Dict[Tuple[int, str, bool], _DecodeGraph] = {}
+        self._twin_failed: set = set()
         # constrained decoding (ops.constrain): the device automaton tables are allocated at the first
         # registration, at a fixed capacity -- the decode graphs capture their pointers
         self.fsm_max_states = int(fsm_max_states)
@@ -338,15 +383,6 @@ class ModelRunner:
         self._fsm_known: Dict[str, int] = {}              # automaton key -> state offset
         self._fsm_tok_key = None
         self.last_fsm_state: Optional[torch.Tensor] = None   # state_out of the latest step, beside last_sampled
-        self._step_state_out: Optional[torch.Tensor] = None
-        self.graphs_fsm: Dict[int, _DecodeGraph] = {}     # constrained twins of the decode buckets (lazy)
-        self._fsm_failed: set = set()
-        # generation log-probabilities: log-probability twins of the decode buckets (lazy), keyed
-        # (bucket, "fused" | "filt" | "fsm") by the sampler they carry; _step_logprob -- the [S] f32
-        # values of the step being launched, beside its sampled ids
-        self.graphs_lp: Dict[Tuple[int, str], _DecodeGraph] = {}
-        self._lp_failed: set = set()
-        self._step_logprob: Optional[torch.Tensor] = None
         self._static = None
         self.graph_pool = None
         self.stats = {"steps": 0, "graph_steps": 0, "tokens": 0, "prefill_steps": 0, "prefill_step_tokens": 0,
@@ -555,7 +591,7 @@ class ModelRunner:
     def _has_filters(si: StepInputs) -> bool:
         return bool((si.top_k > 0).any() or (si.top_p < 1).any())
 
-    def logits_and_sample(self, si: StepInputs) -> torch.Tensor:
+    def logits_and_sample(self, si: StepInputs) -> Sampled:
         """Forward the step, then sample one token per ``si.logits_idx`` row: fused into the LM head
         where it applies (no top-k / top-p rows), else logits -> sampler."""
         state = None
@@ -563,46 +599,40 @@ class ModelRunner:
             state = self._resolve_fsm(self._to_dev(si.fsm_state))
         h = self._hidden(si)
         hs = h.index_select(0, self._to_dev(si.logits_idx))
-        lp = si.want_logprobs
-        if state is not None:              # constrained rows: logits -> masked sampler, as top-k / top-p steps
-            return self._sample_logits(self.model.logits(hs), si, state)
-        if not self._has_filters(si) and self._shard_sampling():
+        filt = self._has_filters(si)
+        kind = sampler_kind(state is not None, filt, self._shard_sampling(), self._fused_sampling(hs))
+        if kind == "shard":
             self.stats["vocab_parallel_sample_steps"] = self.stats.get("vocab_parallel_sample_steps", 0) + 1
-            return self.model.sample_vocab_parallel(hs, self._to_dev(si.temps), self._to_dev(si.seeds))
-        if not self._has_filters(si) and self._fused_sampling(hs):
+        elif kind == "fused":
             self.stats["fused_lm_head_steps"] = self.stats.get("fused_lm_head_steps", 0) + 1
-            if lp:                         # the same tokens, and their log-probabilities, still without logits
-                out, self._step_logprob = ops.lm_head_sample_logprob(
-                    hs, self.model.lm_weight(), self._to_dev(si.temps), self._to_dev(si.seeds), wt=self._lm_tiled())
-                return out
-            return ops.lm_head_sample(hs, self.model.lm_weight(), self._to_dev(si.temps), self._to_dev(si.seeds),
-                                      wt=self._lm_tiled())
-        return self._sample_logits(self.model.logits(hs), si)
+        return self._sample(hs, kind, self._to_dev(si.temps), self._to_dev(si.seeds),
+                            self._to_dev(si.top_k) if filt else None, self._to_dev(si.top_p) if filt else None,
+                            state, si.want_logprobs)
 
-    def _sample_logits(self, logits: torch.Tensor, si: StepInputs, state: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``sample`` on a step that holds its logits; a step that wants log-probabilities reads them
-        off the same logits right after the (untouched) sampler."""
-        logits = logits.contiguous()
-        out = self.sample(logits, si, state)
-        if si.want_logprobs:
-            self._step_logprob = ops.token_logprobs(logits, out)
-        return out
-
-    def sample(self, logits: torch.Tensor, si: StepInputs, state: Optional[torch.Tensor] = None) -> torch.Tensor:
-        temps = self._to_dev(si.temps)
-        seeds = self._to_dev(si.seeds)
-        if state is not None:
+    def _sample(self, hs: torch.Tensor, kind: str, temps: torch.Tensor, seeds: torch.Tensor,
+                top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
+                state: Optional[torch.Tensor] = None, lp: bool = False) -> Sampled:
+        """The one sampling stage, of eager steps and captured graphs alike: one token per hidden row
+        ``hs`` through the sampler ``kind`` (see ``sampler_kind``).  ``lp``: the log-probability form
+        -- the same tokens, the fused LM head still without logits, a step that holds its logits
+        reading the values off them right after the (untouched) sampler."""
+        m = self.model
+        if kind == "shard":
+            return Sampled(m.sample_vocab_parallel(hs, temps, seeds))
+        if kind == "fused":
+            if lp:
+                out, logprob = ops.lm_head_sample_logprob(hs, m.lm_weight(), temps, seeds, wt=self._lm_tiled())
+                return Sampled(out, None, logprob)
+            return Sampled(ops.lm_head_sample(hs, m.lm_weight(), temps, seeds, wt=self._lm_tiled()))
+        logits = m.logits(hs).contiguous()
+        state_out = None
+        if kind == "fsm":
             if self.fsm is None:
                 raise RuntimeError("a constrained step without a registered automaton")
-            filt = self._has_filters(si)
-            out, self._step_state_out = ops.sample_constrained(
-                logits.contiguous(), temps, seeds, state, self.fsm,
-                top_k=self._to_dev(si.top_k) if filt else None, top_p=self._to_dev(si.top_p) if filt else None)
-            return out
-        if self._has_filters(si):   # device-side top-k/top-p threshold
-            return ops.sample(logits.contiguous(), temps, seeds, top_k=self._to_dev(si.top_k),
-                              top_p=self._to_dev(si.top_p))
-        return ops.sample(logits.contiguous(), temps, seeds)
+            out, state_out = ops.sample_constrained(logits, temps, seeds, state, self.fsm, top_k=top_k, top_p=top_p)
+        else:                       # device-side top-k / top-p threshold when given
+            out = ops.sample(logits, temps, seeds, top_k=top_k, top_p=top_p)
+        return Sampled(out, state_out, ops.token_logprobs(logits, out) if lp else None)
 
     def execute(self, si: StepInputs) -> List[int]:
         """Run one step; returns the sampled token per entry of ``si.logits_idx``."""
@@ -643,29 +673,27 @@ class ModelRunner:
                 start_ev.record()
             else:
                 start_ev = None
-        graph = False
-        if (self.use_graphs and si.num_prefill_tokens == 0 and 0 < si.num_decode <= self.max_decode_batch
-                and not self._fused_graph_needs_eager(si)):
+        G = None
+        if self.use_graphs and si.num_prefill_tokens == 0 and 0 < si.num_decode <= self.max_decode_batch:
+            G = self._decode_graph(si)
+        graph = G is not None
+        if graph:
             with marker(f"decode.graph[{si.num_decode}]"):
-                out = self._graph_decode(si)
-            graph = True
+                out, so, lpv = self._graph_decode(si, G)
         else:
             with marker(f"forward.eager[{len(si.ids)}]"):
                 if si.num_prefill_tokens and si.pwork is None and self.on_gpu:
                     si.pwork = prefill_plan(si.cu_q, si.ctx_p, self.G, self.model.hkv)
                 self._stage_inputs(si)
                 try:
-                    out = self.logits_and_sample(si)
+                    out, so, lpv = self.logits_and_sample(si)
                 finally:
                     self._staged = None
         n = len(si.logits_idx)
         self.last_sampled[:n].copy_(out[:n].to(torch.int32), non_blocking=True)
-        lpv = None
         if si.want_logprobs:
-            lpv, self._step_logprob = self._step_logprob, None
             self.stats["logprob_steps"] += 1
         if si.fsm_state is not None:
-            so, self._step_state_out = self._step_state_out, None
             self.last_fsm_state[:n].copy_(so[:n], non_blocking=True)
             self.stats["constrained_steps"] += 1
             self.stats["constrained_tokens"] += int((si.fsm_state != -1).sum())
@@ -724,9 +752,7 @@ class ModelRunner:
         if self.on_gpu:
             torch.cuda.synchronize(self.device)
         self.graphs.clear()
-        self.graphs_filt.clear()
-        self.graphs_fsm.clear()
-        self.graphs_lp.clear()
+        self.twins.clear()
         self.use_graphs = False
         self._dual = False
 
@@ -788,8 +814,11 @@ class ModelRunner:
                                                          self.device)
         return self._dual
 
-    def _run_static(self, B: int, filtered: bool = False, fsm: bool = False, lp: bool = False) -> torch.Tensor:
+    def _run_static(self, B: int, kind: Optional[str] = None, lp: bool = False) -> Tuple[str, Sampled]:
+        """One decode step of bucket B on the static inputs, sampled by ``kind`` (None: the bucket's
+        default sampler, decided here and returned)."""
         s = self._static
+        fsm = kind == "fsm"
         self._gather_pending(s["ids"], s["src"][:B], 0)
         if fsm:      # carry codes -> states, in place, before the sampler of this graph writes state_out
             s["fsm"][:B].copy_(self._resolve_fsm(s["fsm"][:B]))
@@ -804,33 +833,24 @@ class ModelRunner:
             meta = AttentionMetadata(slots=s["slots"][:B], num_prefill_tokens=0, num_decode=B,
                                      ctx_lens_d=s["ctx"][:B], block_tables_d=s["bt"][:B], decode_ws=self.decode_ws)
             h = self.model.forward(s["ids"][:B], s["pos"][:B], meta, self.kv)
-        if fsm:
-            # the constrained twin: mask, then the top-k / top-p threshold (unfiltered rows leave it
-            # after reading their parameters), then the sampler and the state update
-            logits = self.model.logits(h)
-            out, self._step_state_out = ops.sample_constrained(
-                logits, s["temps"][:B], s["seeds"][:B], s["fsm"][:B], self.fsm,
-                top_k=s["top_k"][:B], top_p=s["top_p"][:B])
-            if lp:
-                self._step_logprob = ops.token_logprobs(logits, out)
-            return out
-        if not filtered:
-            if self._shard_sampling():     # TP: top-k / top-p rows of this bucket replay eagerly
-                return self.model.sample_vocab_parallel(h, s["temps"][:B], s["seeds"][:B])
-            if self._fused_sampling(h):
-                if lp:
-                    out, self._step_logprob = ops.lm_head_sample_logprob(
-                        h, self.model.lm_weight(), s["temps"][:B], s["seeds"][:B], wt=self._lm_tiled())
-                    return out
-                return ops.lm_head_sample(h, self.model.lm_weight(), s["temps"][:B], s["seeds"][:B],
-                                          wt=self._lm_tiled())
-        logits = self.model.logits(h)
-        # the top-k/top-p threshold kernel is always in the graph: unfiltered rows (k=0, p=1) exit
-        # after reading their parameters
-        out = ops.sample(logits, s["temps"][:B], s["seeds"][:B], top_k=s["top_k"][:B], top_p=s["top_p"][:B])
-        if lp:
-            self._step_logprob = ops.token_logprobs(logits, out)
-        return out
+        if kind is None:
+            kind = default_graph_kind(self._shard_sampling(), self._fused_sampling(h))
+        # the top-k / top-p threshold kernel is always in a graph that samples from logits: unfiltered
+        # rows (k=0, p=1) exit after reading their parameters; under TP such rows replay eagerly
+        filt = kind in ("fsm", "logits")
+        return kind, self._sample(h, kind, s["temps"][:B], s["seeds"][:B], s["top_k"][:B] if filt else None,
+                                  s["top_p"][:B] if filt else None, s["fsm"][:B] if fsm else None, lp)
+
+    def _capture(self, B: int, kind: Optional[str] = None, lp: bool = False) -> _DecodeGraph:
+        for _ in range(2):      # warm up (allocator + hipBLASLt heuristics) outside the capture
+            self._run_static(B, kind, lp)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self.graph_pool):
+            kind, sampled = self._run_static(B, kind, lp)
+        if self.graph_pool is None:
+            self.graph_pool = g.pool()
+        return _DecodeGraph(g, B, sampled.out, kind in ("shard", "fused"), sampled.state_out, sampled.logprob)
 
     def capture_graphs(self) -> None:
         if not self.use_graphs:
@@ -839,95 +859,51 @@ class ModelRunner:
             self._alloc_static()
         torch.cuda.synchronize()
         for B in sorted(self.graph_sizes, reverse=True):
-            # warm up (allocator + hipBLASLt heuristics) outside the capture
-            for _ in range(2):
-                self._run_static(B)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self.graph_pool):
-                out = self._run_static(B)
-            if self.graph_pool is None:
-                self.graph_pool = g.pool()
-            fused = self._shard_sampling() or self._fused_sampling(
-                torch.empty((B, self.model.cfg.hidden_size), dtype=torch.bfloat16, device=self.device))
-            self.graphs[B] = _DecodeGraph(g, B, out, fused)
+            self.graphs[B] = self._capture(B)
         torch.cuda.synchronize()
         logger.info(f"captured decode hipGraphs for batch sizes {sorted(self.graphs)}")
 
-    def _fused_graph_needs_eager(self, si: StepInputs) -> bool:
-        """A decode step its bucket's graph cannot sample: top-k / top-p rows when the graph samples
-        inside the LM head, or constrained rows (any graph).  At TP=1 it replays the bucket's TWIN
-        (filtered: logits -> threshold -> sampler; constrained: logits -> masked threshold -> masked
-        sampler + state update), captured on the first such step; under TP it runs eagerly.  A step
-        that wants log-probabilities always needs a twin (``graphs_lp``): the bucket's sampler in its
-        log-probability form."""
-        fsm = si.fsm_state is not None
-        lp = si.want_logprobs
-        if not fsm and not lp and not self._has_filters(si):
-            return False
+    def _decode_graph(self, si: StepInputs) -> Optional[_DecodeGraph]:
+        """The captured graph that runs this pure-decode step (``graph_plan``), or None: eagerly.  A
+        twin is captured by the first step that needs it; one that cannot be (e.g. out of memory after
+        the KV pool took HBM) leaves its steps on the eager path for good."""
         if not self.graphs:
             self.capture_graphs()
         B = self._bucket(si.num_decode)
-        G = self.graphs.get(B)
-        if G is None or not (G.fused or fsm or lp):
-            return False
-        if getattr(self.model, "tp_size", 1) > 1:
-            return True
-        if lp:      # a log-probability step replays the log-probability twin of the sampler it needs
-            key = (B, self._lp_kind(si, G))
-            twins, failed = self.graphs_lp, self._lp_failed
-        else:
-            key = B
-            twins, failed = (self.graphs_fsm, self._fsm_failed) if fsm else (self.graphs_filt, self._filt_failed)
-        if key in failed:
-            return True
-        if key not in twins:
+        G = self.graphs[B]
+        plan = graph_plan(si.fsm_state is not None, self._has_filters(si), si.want_logprobs, G.fused,
+                          getattr(self.model, "tp_size", 1) > 1)
+        if plan == DEFAULT_GRAPH:
+            return G
+        if plan == EAGER:
+            return None
+        key = (B, *plan)
+        if key in self._twin_failed:
+            return None
+        if key not in self.twins:
             try:
-                self._capture_twin(B, fsm, lp=key[1] if lp else None)
-            except Exception as e:  # noqa: BLE001 - e.g. out of memory after the KV pool took HBM
-                # (ADVICE r5): this bucket's filtered / constrained rows stay on the eager path for good
-                kind = ("constrained" if fsm else "filtered") if not lp else f"log-probability ({key[1]})"
-                logger.warning(f"{kind} decode graph for batch {B} not captured ({e}); running it eagerly")
-                failed.add(key)
+                self._capture_twin(key)
+            except Exception as e:  # noqa: BLE001
+                logger.warning(f"decode graph twin {key} not captured ({e}); running its steps eagerly")
+                self._twin_failed.add(key)
                 torch.cuda.synchronize(self.device)
-                return True
-        return False
+                return None
+        return self.twins[key]
 
-    def _lp_kind(self, si: StepInputs, G: _DecodeGraph) -> str:
-        """Which sampler a log-probability step of this bucket needs: the masked one, the logits one
-        (top-k / top-p rows, or a bucket that never samples in the LM head), or the fused LM head."""
-        if si.fsm_state is not None:
-            return "fsm"
-        return "filt" if self._has_filters(si) or not G.fused else "fused"
-
-    def _capture_twin(self, B: int, fsm: bool, lp: Optional[str] = None) -> None:
+    def _capture_twin(self, key: Tuple[int, str, bool]) -> None:
         """Capture mid-serving: the static inputs still hold the step in flight, so the warm-up and
         capture passes run with every KV slot masked (< 0: no cache write), no pending-token
         gather and no automaton state -- they must not rewrite live sequences' KV -- and the inputs
         are restored after."""
+        B, kind, lp = key
         s = self._static
         saved = (s["slots"][:B].clone(), s["src"][:B].clone(), s["fsm"][:B].clone())
         s["slots"][:B].fill_(-1)
         s["src"][:B].fill_(-1)
         s["fsm"][:B].fill_(-1)
-        filtered = lp != "fused"                  # lp: the twin's sampler ("fused" | "filt" | "fsm"), None: no values
         try:
-            for _ in range(2):
-                self._run_static(B, filtered=filtered, fsm=fsm, lp=lp is not None)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self.graph_pool):
-                out = self._run_static(B, filtered=filtered, fsm=fsm, lp=lp is not None)
-            if lp is not None:
-                self.graphs_lp[(B, lp)] = _DecodeGraph(g, B, out, lp == "fused", self._step_state_out if fsm else None,
-                                                       self._step_logprob)
-            elif fsm:
-                self.graphs_fsm[B] = _DecodeGraph(g, B, out, False, self._step_state_out)
-            else:
-                self.graphs_filt[B] = _DecodeGraph(g, B, out, False)
+            self.twins[key] = self._capture(B, kind, lp)
         finally:                                  # the step in flight keeps its inputs either way
-            self._step_state_out = None
-            self._step_logprob = None
             s["slots"][:B].copy_(saved[0])
             s["src"][:B].copy_(saved[1])
             s["fsm"][:B].copy_(saved[2])
@@ -939,18 +915,8 @@ class ModelRunner:
                 return b
         return self.graph_sizes[-1]
 
-    def _graph_decode(self, si: StepInputs) -> List[int]:
-        if not self.graphs:
-            self.capture_graphs()
-        n = si.num_decode
-        B = self._bucket(n)
-        G = self.graphs[B]
-        if si.want_logprobs:
-            G = self.graphs_lp[(B, self._lp_kind(si, G))]
-        elif si.fsm_state is not None:
-            G = self.graphs_fsm[B]
-        elif G.fused and self._has_filters(si) and B in self.graphs_filt:
-            G = self.graphs_filt[B]
+    def _graph_decode(self, si: StepInputs, G: _DecodeGraph) -> Sampled:
+        n, B = si.num_decode, G.B
         S, W = self.max_decode_batch, self.max_blocks
         self._pinned_i32, self._pinned_f, self._pinned_l = self._pinned_sets[self._pin_flip]
         self._pin_flip ^= 1
@@ -987,6 +953,4 @@ class ModelRunner:
         s["seeds"].copy_(self._pinned_l, non_blocking=True)
         G.graph.replay()
         self.stats["graph_steps"] += 1
-        self._step_state_out = G.state_out
-        self._step_logprob = G.logprob
-        return G.out[:n]
+        return Sampled(G.out[:n], G.state_out, G.logprob)

@@ -110,14 +110,26 @@ def fused_lm_head_ok(h: torch.Tensor, w: torch.Tensor) -> bool:
     return mode == "force" or M >= FUSED_LM_HEAD_MIN_M or _stream_ok(M)
 
 
-def lm_head_stream_sample(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
-                          vvalid: Optional[int] = None, voff: int = 0, pairs: bool = False,
-                          out: Optional[torch.Tensor] = None, nf: Optional[int] = None,
-                          rowmajor: Optional[bool] = None, ring2: Optional[bool] = None) -> torch.Tensor:
-    """The weight-streaming fused LM head + sampler (M <= 128 rows): ``w`` [Vpad, K] row-major (or,
-    ``rowmajor=False``, its ``ops.gemm.tile_weight`` copy of the [Vpad, K] weight), global rows
-    voff .. voff+vvalid-1 then padding.  Returns int32 tokens [M], or (``pairs``) the [M, 2]
-    (score bits, global id) shard candidates of :func:`sample_shard`."""
+def _use_stream(M: int, Vpad: int) -> bool:
+    """The route of every fused LM head over ``Vpad`` weight rows: the weight-streaming kernel (decode
+    sizes whose vocab tiles divide ``Vpad``) or, False, the 256-row tile kernel."""
+    import os
+    return _stream_ok(M) and os.environ.get("PENNY_FUSED_LM_HEAD") != "force" and Vpad % (16 * stream_cfg(M)[0]) == 0
+
+
+def _temps_seeds(temperatures: torch.Tensor, seeds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The samplers' per-row arguments as the kernels read them; the caller keeps them alive across the launch."""
+    return temperatures.to(torch.float32).contiguous(), seeds.contiguous()
+
+
+def _stream_call(fn: str, h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
+                 vvalid: Optional[int], voff: int, nf: Optional[int], rowmajor: Optional[bool],
+                 ring2: Optional[bool], planes: int, outs: tuple) -> list:
+    """One launch of a streaming LM head ``fn``: ``w`` [Vpad, K] row-major or its tiled copy, ``nf`` /
+    ``ring2`` from ``stream_cfg`` unless given, and a workspace of ``planes`` [M, P] partial planes (2 per
+    16 * nf vocab rows: the most any wave split leaves).  ``outs``: per output of ``fn`` None (not asked
+    for), the tensor to fill, or the (shape, dtype) to allocate -- after the workspace, the order a
+    captured graph's pool has always seen.  Returns the outputs."""
     M, K = h.shape
     Vpad = w.shape[0] * (16 if w.dim() == 4 else 1)
     vvalid = Vpad if vvalid is None else vvalid
@@ -126,17 +138,38 @@ def lm_head_stream_sample(h: torch.Tensor, w: torch.Tensor, temperatures: torch.
     rowmajor = (w.dim() == 2) if rowmajor is None else rowmajor
     ring2 = d_r2 if ring2 is None else ring2
     P = Vpad // (16 * nf) * 2
-    ws = torch.empty((2 * M * P,), dtype=torch.float32, device=h.device)
-    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
-    if pairs:
-        res = torch.empty((M, 2), dtype=torch.int32, device=h.device)
-        o, pr = None, res
-    else:
-        res = torch.empty((M,), dtype=torch.int32, device=h.device) if out is None else out
-        o, pr = res, None
-    N.call("penny_lm_head_stream_sample", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, int(vvalid), int(voff),
-           N.ptr(temps), N.ptr(sd), N.ptr(ws), N.ptr(o), N.ptr(pr), int(nf), int(rowmajor), int(ring2), N.stream())
-    return res
+    ws = torch.empty((planes * M * P,), dtype=torch.float32, device=h.device)
+    temps, sd = _temps_seeds(temperatures, seeds)
+    outs = [torch.empty(o[0], dtype=o[1], device=h.device) if isinstance(o, tuple) else o for o in outs]
+    N.call(fn, N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, int(vvalid), int(voff), N.ptr(temps), N.ptr(sd), N.ptr(ws),
+           *map(N.ptr, outs), int(nf), int(rowmajor), int(ring2), N.stream())
+    return outs
+
+
+def _tile_call(fn: str, h: torch.Tensor, w: torch.Tensor, planes: int, mid: tuple, outs: tuple) -> None:
+    """One launch of a 256-row tile LM head ``fn`` over ``w`` [Vpad, K]: ``mid`` are its arguments (tensors
+    or ints) between Vpad and the workspace of ``planes`` [M, 2 * Vpad / 256] partial planes, ``outs`` the
+    tensors after it."""
+    M, K = h.shape
+    Vpad = w.shape[0]
+    ws = torch.empty((planes * M * 2 * (Vpad // 256),), dtype=torch.float32, device=h.device)
+    mid = [N.ptr(x) if torch.is_tensor(x) else int(x) for x in mid]
+    N.call(fn, N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, *mid, N.ptr(ws), *map(N.ptr, outs), N.stream())
+
+
+def lm_head_stream_sample(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
+                          vvalid: Optional[int] = None, voff: int = 0, pairs: bool = False,
+                          out: Optional[torch.Tensor] = None, nf: Optional[int] = None,
+                          rowmajor: Optional[bool] = None, ring2: Optional[bool] = None) -> torch.Tensor:
+    """The weight-streaming fused LM head + sampler (M <= 128 rows): ``w`` [Vpad, K] row-major (or,
+    ``rowmajor=False``, its ``ops.gemm.tile_weight`` copy of the [Vpad, K] weight), global rows
+    voff .. voff+vvalid-1 then padding.  Returns int32 tokens [M], or (``pairs``) the [M, 2]
+    (score bits, global id) shard candidates of :func:`sample_shard`."""
+    M = h.shape[0]
+    tok = ((M,), torch.int32) if out is None else out
+    res = _stream_call("penny_lm_head_stream_sample", h, w, temperatures, seeds, vvalid, voff, nf, rowmajor, ring2, 2,
+                       (None, ((M, 2), torch.int32)) if pairs else (tok, None))
+    return res[1] if pairs else res[0]
 
 
 def lm_head_sample(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
@@ -150,19 +183,14 @@ def lm_head_sample(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor,
     token_agreement).  No top-k / top-p (those rows need the whole distribution: use ``sample``).
     ``wt``: the fragment-tiled copy of ``w`` (``ops.gemm.tile_weight``), streamed instead of ``w`` by
     the decode-size kernel when given."""
-    import os
-    M, K = h.shape
-    V = w.shape[0]
+    M = h.shape[0]
     if not N.use_native(h):
         import torch.nn.functional as F
         return sample(F.linear(h.float(), w.float()).to(h.dtype), temperatures, seeds, out=out)
-    if _stream_ok(M) and os.environ.get("PENNY_FUSED_LM_HEAD") != "force" and V % (16 * stream_cfg(M)[0]) == 0:
+    if _use_stream(M, w.shape[0]):
         return lm_head_stream_sample(h, wt if wt is not None else w, temperatures, seeds, out=out)
     out = torch.empty((M,), dtype=torch.int32, device=h.device) if out is None else out
-    ws = torch.empty((2 * M * 2 * (V // 256),), dtype=torch.float32, device=h.device)
-    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
-    N.call("penny_lm_head_sample", N.ptr(h), h.stride(0), N.ptr(w), K, M, V, N.ptr(temps), N.ptr(sd), N.ptr(ws),
-           N.ptr(out), N.stream())
+    _tile_call("penny_lm_head_sample", h, w, 2, _temps_seeds(temperatures, seeds), (out,))
     return out
 
 
@@ -226,21 +254,10 @@ def lm_head_stream_sample_logprob(h: torch.Tensor, w: torch.Tensor, temperatures
                                   ring2: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """:func:`lm_head_stream_sample` (same arguments, same tokens) that also returns each token's
     log-probability: (ids int32 [M], logprob f32 [M])."""
-    M, K = h.shape
-    Vpad = w.shape[0] * (16 if w.dim() == 4 else 1)
-    vvalid = Vpad if vvalid is None else vvalid
-    d_nf, d_r2 = stream_cfg(M)
-    nf = d_nf if nf is None else nf
-    rowmajor = (w.dim() == 2) if rowmajor is None else rowmajor
-    ring2 = d_r2 if ring2 is None else ring2
-    P = Vpad // (16 * nf) * 2
-    ws = torch.empty((5 * M * P,), dtype=torch.float32, device=h.device)
-    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
-    out = torch.empty((M,), dtype=torch.int32, device=h.device) if out is None else out
-    logprob = torch.empty((M,), dtype=torch.float32, device=h.device) if logprob is None else logprob
-    N.call("penny_lm_head_stream_sample_logprob", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, int(vvalid), int(voff),
-           N.ptr(temps), N.ptr(sd), N.ptr(ws), N.ptr(out), N.ptr(logprob), int(nf), int(rowmajor), int(ring2),
-           N.stream())
+    M = h.shape[0]
+    out, logprob = _stream_call("penny_lm_head_stream_sample_logprob", h, w, temperatures, seeds, vvalid, voff, nf,
+                                rowmajor, ring2, 5, (((M,), torch.int32) if out is None else out,
+                                                     ((M,), torch.float32) if logprob is None else logprob))
     return out, logprob
 
 
@@ -258,7 +275,7 @@ def lm_head_sample_logprob(h: torch.Tensor, w: torch.Tensor, temperatures: torch
     ``LOGPROB_UNFUSED_ROWS`` through logits + sampler + :func:`token_logprobs` instead (faster there,
     tokens then reproducible only up to logit rounding)."""
     import os
-    M, K = h.shape
+    M = h.shape[0]
     Vpad = w.shape[0]
     vvalid = Vpad if vvalid is None else int(vvalid)
     if not 0 < vvalid <= Vpad or voff < 0:
@@ -284,15 +301,13 @@ def lm_head_sample_logprob(h: torch.Tensor, w: torch.Tensor, temperatures: torch
         if voff:
             ids.add_(int(voff))
         return ids, lp
-    if _stream_ok(M) and os.environ.get("PENNY_FUSED_LM_HEAD") != "force" and Vpad % (16 * stream_cfg(M)[0]) == 0:
+    if _use_stream(M, Vpad):
         return lm_head_stream_sample_logprob(h, wt if wt is not None else w, temperatures, seeds, vvalid=vvalid,
                                              voff=voff, out=out, logprob=logprob)
     out = torch.empty((M,), dtype=torch.int32, device=h.device) if out is None else out
     logprob = torch.empty((M,), dtype=torch.float32, device=h.device) if logprob is None else logprob
-    ws = torch.empty((5 * M * 2 * (Vpad // 256),), dtype=torch.float32, device=h.device)
-    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
-    N.call("penny_lm_head_sample_logprob", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, vvalid, int(voff),
-           N.ptr(temps), N.ptr(sd), N.ptr(ws), N.ptr(out), N.ptr(logprob), N.stream())
+    _tile_call("penny_lm_head_sample_logprob", h, w, 5, (vvalid, voff, *_temps_seeds(temperatures, seeds)),
+               (out, logprob))
     return out, logprob
 
 
@@ -337,17 +352,12 @@ def lm_head_sample_shard(h: torch.Tensor, w_pad: torch.Tensor, vvalid: int, voff
                          seeds: torch.Tensor, wt: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused LM head + sampler on one vocab shard: ``w_pad`` [Vpad, K] (Vpad % 256 == 0) holds global
     rows voff .. voff+vvalid-1 then padding -> pairs [M, 2] as :func:`sample_shard`."""
-    import os
-    M, K = h.shape
-    Vpad = w_pad.shape[0]
-    if _stream_ok(M) and os.environ.get("PENNY_FUSED_LM_HEAD") != "force" and Vpad % (16 * stream_cfg(M)[0]) == 0:
+    M = h.shape[0]
+    if _use_stream(M, w_pad.shape[0]):
         return lm_head_stream_sample(h, wt if wt is not None else w_pad, temperatures, seeds, vvalid=vvalid,
                                      voff=voff, pairs=True)
     pairs = torch.empty((M, 2), dtype=torch.int32, device=h.device)
-    ws = torch.empty((2 * M * 2 * (Vpad // 256),), dtype=torch.float32, device=h.device)
-    temps, sd = temperatures.to(torch.float32).contiguous(), seeds.contiguous()   # alive across the launch
-    N.call("penny_lm_head_sample_shard", N.ptr(h), h.stride(0), N.ptr(w_pad), K, M, Vpad, int(vvalid), int(voff),
-           N.ptr(temps), N.ptr(sd), N.ptr(ws), N.ptr(pairs), N.stream())
+    _tile_call("penny_lm_head_sample_shard", h, w_pad, 2, (vvalid, voff, *_temps_seeds(temperatures, seeds)), (pairs,))
     return pairs
 
 
@@ -396,7 +406,7 @@ def lm_head_logprobs(h: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, vv
     logprob -inf).  Returns logprob [M] f32, or (``return_stats``) stats [M, 4] f32 = {max logit,
     sum exp(l - max), target logit (-inf when absent from this shard), argmax id as int32 bits,
     ties to the smallest id} -- what :func:`merge_logprob_stats` combines across shards."""
-    M, K = h.shape
+    M = h.shape[0]
     Vpad = w.shape[0]
     vvalid = Vpad if vvalid is None else int(vvalid)
     if not 0 < vvalid <= Vpad or voff < 0:
@@ -405,9 +415,7 @@ def lm_head_logprobs(h: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, vv
     if fused_logprob_ok(h, w):
         stats = torch.empty((M, 4), dtype=torch.float32, device=h.device)
         lp = None if return_stats else torch.empty((M,), dtype=torch.float32, device=h.device)
-        ws = torch.empty((4 * M * 2 * (Vpad // 256),), dtype=torch.float32, device=h.device)
-        N.call("penny_lm_head_logprob", N.ptr(h), h.stride(0), N.ptr(w), K, M, Vpad, vvalid, int(voff), N.ptr(tg),
-               N.ptr(ws), N.ptr(stats), N.ptr(lp), N.stream())
+        _tile_call("penny_lm_head_logprob", h, w, 4, (vvalid, voff, tg), (stats, lp))
         return stats if return_stats else lp
     from .gemm import linear
     lf = linear(h, w[:vvalid]).float()          # logits in the activation dtype (bf16 on the device)

@@ -344,7 +344,8 @@ def test_engine_constrained_eager_graph_overlap_sync(tok):
     eager, e0 = _engine_run(tok, graph=False, overlap=True)
     assert e0.stats()["constrained_steps"] > 0 and e0.runner.stats["graph_steps"] == 0
     graph, e1 = _engine_run(tok, graph=True, overlap=True, model=e0.model)
-    assert e1.runner.graphs_fsm and not e1.runner._fsm_failed and e1.runner.stats["graph_steps"] > 0
+    r1 = e1.runner
+    assert any(k[1:] == ("fsm", False) for k in r1.twins) and not r1._twin_failed and r1.stats["graph_steps"] > 0
     sync, e2 = _engine_run(tok, graph=False, overlap=False, model=e0.model)
     same_g = sum(x == y for x, y in zip(eager, graph))
     same_s = sum(x == y for x, y in zip(eager, sync))

@@ -256,7 +256,7 @@ def on_off(graph, overlap, automaton, **kw):
     e0 = _engine(graph, overlap, **kw)
     off, _ = R.run_scenario(e0, automaton, False, "g")
     s0 = R.pool_state(e0)
-    assert e0.stats()["logprob_steps"] == 0 and not e0.runner.graphs_lp
+    assert e0.stats()["logprob_steps"] == 0 and not any(lp for _, _, lp in e0.runner.twins)
     e1 = _engine(graph, overlap, **kw)
     on, outs = R.run_scenario(e1, automaton, True, "g")
     return off, on, outs, e1, (s0, R.pool_state(e1))
@@ -274,8 +274,8 @@ def test_engine_tokens_unchanged_aligned_and_drift(mode, automaton):
     st = eng.runner.stats
     assert st["logprob_steps"] > 0
     if graph:    # the log-probability twins were captured lazily and replayed; the default graphs stand
-        assert eng.runner.graphs_lp and not eng.runner._lp_failed and st["graph_steps"] > 0
-        assert {k[1] for k in eng.runner.graphs_lp} >= {"fused", "fsm"}
+        assert not eng.runner._twin_failed and st["graph_steps"] > 0
+        assert {kind for _, kind, lp in eng.runner.twins if lp} >= {"fused", "fsm"}
     drift = R.score_drift(eng, on)
     print(f"{mode}: generation vs score() drift = {drift:.4e} nats, spec {eng.spec_stats}")
     assert drift <= 2 * GEN_DRIFT_BF16
