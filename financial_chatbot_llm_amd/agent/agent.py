@@ -60,8 +60,12 @@ class LLMAgent:
                  today_fn: Callable[[], _dt.date] = _dt.date.today,
                  system_prompt: Optional[str] = None, tool_prompt: Optional[str] = None,
                  max_transaction_tokens: Optional[int] = config.MAX_TRANSACTION_TOKENS,
-                 decide_logprobs: bool = False, decide_confidence_threshold: float = 0.5):
+                 decide_logprobs: bool = False, decide_confidence_threshold: float = 0.5,
+                 respond_penalties: Optional[Dict[str, float]] = None):
         self.llm = llm
+        # repetition_penalty / presence_penalty / frequency_penalty of the streamed respond call
+        # (ServingConfig.respond_penalties); the decide call never gets them: its output is JSON
+        self.respond_penalties: Dict[str, float] = dict(respond_penalties or {})
         # decide confidence (ServingConfig.decide_logprobs): the decide call asks for the sampled
         # tokens' log-probabilities and exp(mean) goes to the metrics registry
         self.decide_logprobs = bool(decide_logprobs)
@@ -200,7 +204,7 @@ class LLMAgent:
         parts = []
         async for piece in self.llm.astream(self.respond_messages(state), temperature=self.temperature,
                                             max_tokens=self.max_response_tokens, purpose="respond",
-                                            ephemeral_kv=bool(state["tool_results"])):
+                                            ephemeral_kv=bool(state["tool_results"]), **self.respond_penalties):
             parts.append(piece)
         state["final_response"] = "".join(parts)
         logger.info("Final response generated")
@@ -258,7 +262,7 @@ class LLMAgent:
         yield {"type": "status", "message": "Generating response..."}
         async for piece in self.llm.astream(self.respond_messages(state), temperature=self.temperature,
                                             max_tokens=self.max_response_tokens, purpose="respond",
-                                            ephemeral_kv=bool(state["tool_results"])):
+                                            ephemeral_kv=bool(state["tool_results"]), **self.respond_penalties):
             if piece:
                 yield {"type": "response_chunk", "content": piece}
         yield {"type": "complete", "message": "Query processing completed"}

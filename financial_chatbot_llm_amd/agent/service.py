@@ -24,8 +24,10 @@ logger = get_logger(__name__)
 
 class LLMService:
     def __init__(self, llm: LLMBackend, system_prompt: Optional[str] = None,
-                 temperature: float = config.DEFAULT_TEMPERATURE, max_response_tokens: int = 512):
+                 temperature: float = config.DEFAULT_TEMPERATURE, max_response_tokens: int = 512,
+                 respond_penalties: Optional[dict] = None):
         self.llm = llm
+        self.respond_penalties = dict(respond_penalties or {})     # ServingConfig.respond_penalties
         self.system_prompt = system_prompt if system_prompt is not None else _load_system_prompt()
         self.temperature = temperature
         self.max_response_tokens = max_response_tokens
@@ -41,7 +43,7 @@ class LLMService:
         try:
             return self.llm.astream(self.messages(message, context, chat_history, system_prompt),
                                     temperature=self.temperature, max_tokens=self.max_response_tokens,
-                                    purpose="respond")
+                                    purpose="respond", **self.respond_penalties)
         except Exception as e:  # noqa: BLE001
             logger.error(f"Error streaming LLM response: {e}")
             raise

@@ -756,6 +756,72 @@ def bench_constrained_sample(dev, Ms=(16, 64, 128, 256), V: int = 128256, K: int
     return out
 
 
+def bench_penalty_sample(dev, Ms=(16, 64, 128, 256), V: int = 128256, K: int = 4096) -> List[Dict]:
+    """Repetition / presence / frequency penalties (ops.penalty, vocab 128256, K 4096), variants timed
+    in interleaved rounds: (a) penny_sample alone against apply + sample with every second row
+    penalised and with no row penalised; (b) the per-step price of one penalised row -- the fused LM
+    head + sampler against logits (the model's LM-head GEMM) + apply + sample; (c) the table kernels:
+    reset for an 8k-token prompt and add of 256 pairs."""
+    from ..ops import gemm, penalty
+    gemm.load_gemm_tuning("llama3-8b")
+    slots = 256
+    t = ops.PenaltyTable(slots, V, dev)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    prompt = torch.randint(0, V, (8192,), generator=g, dtype=torch.int32).to(dev)
+    for s in range(slots):                        # every slot: an 8k-token prompt and 512 emitted tokens
+        penalty.reset(t, s, prompt)
+        penalty.add(t, torch.stack([torch.full((512,), s, dtype=torch.int32),
+                                    torch.randint(0, V, (512,), generator=g, dtype=torch.int32)], 1).to(dev))
+    pairs = torch.stack([torch.arange(256, dtype=torch.int32) % slots,
+                         torch.randint(0, V, (256,), generator=g, dtype=torch.int32)], 1).to(dev)
+    scratch = ops.PenaltyTable(2, V, dev)         # the timed reset / add write here
+    out = []
+    r = interleaved({"reset_8k": lambda: penalty.reset(scratch, 1, prompt),
+                     "add_256": lambda: penalty.add(scratch, pairs % torch.tensor([2, V], device=dev, dtype=torch.int32)),
+                     }, rounds=9, iters=50)
+    out.append({"op": "penalty_table", "V": V, "reset_8k_prompt_us": round(r["reset_8k"], 1),
+                "add_256_pairs_us": round(r["add_256"], 1), "table_MB_per_64_slots": round(64 * t.Vs * 2 / 1e6, 1)})
+    print(json.dumps(out[-1]), flush=True)
+    w = torch.randn((V, K), device=dev).to(torch.bfloat16) * 0.02
+    for M in Ms:
+        x = torch.randn((M, K), device=dev).to(torch.bfloat16)
+        temps = torch.full((M,), 0.7, device=dev)
+        sd = torch.arange(M, dtype=torch.int64, device=dev) * 977
+        logits = gemm.linear(x, w)
+        work = logits.clone()                     # applied in place, as a step without log-probabilities does
+        rows = torch.arange(M, dtype=torch.int32, device=dev)
+        half = torch.where(rows % 2 == 0, rows, torch.full_like(rows, -1))
+        none = torch.full_like(rows, -1)
+        one = none.clone()
+        one[0] = 0
+        pend = torch.full_like(rows, -1)
+        rep, pres, freq = (torch.full((M,), v, device=dev) for v in (1.1, 0.2, 0.1))
+
+        def apply_sample(slot, lg):
+            ops.apply_penalties(lg, slot, pend, rep, pres, freq, t)
+            return ops.sample(lg, temps, sd)
+        r = interleaved({
+            "sample": lambda: ops.sample(logits, temps, sd),
+            "apply_sample_half": lambda: apply_sample(half, work),
+            "apply_sample_none": lambda: apply_sample(none, work),
+            "apply_half": lambda: ops.apply_penalties(work, half, pend, rep, pres, freq, t),
+            "fused_lm_head": lambda: ops.lm_head_sample(x, w, temps, sd),
+            "logits_plus_pen": lambda: apply_sample(one, gemm.linear(x, w)),
+            "logits_only": lambda: gemm.linear(x, w),
+        }, rounds=9, iters=50)
+        same = bool(torch.equal(apply_sample(none, logits.clone()), ops.sample(logits, temps, sd)))
+        out.append({"op": "penalty_sample", "M": M, "V": V, "K": K, "sample_us": round(r["sample"], 1),
+                    "apply_sample_half_rows_us": round(r["apply_sample_half"], 1),
+                    "apply_sample_no_rows_us": round(r["apply_sample_none"], 1),
+                    "apply_half_rows_us": round(r["apply_half"], 1),
+                    "fused_lm_head_us": round(r["fused_lm_head"], 1), "logits_us": round(r["logits_only"], 1),
+                    "logits_plus_apply_sample_us": round(r["logits_plus_pen"], 1),
+                    "step_price_us": round(r["logits_plus_pen"] - r["fused_lm_head"], 1),
+                    "unpenalised_rows_equal_sample": same})
+        print(json.dumps(out[-1]), flush=True)
+    return out
+
+
 def bench_lm_head_sample_logprob(dev, Ms=(16, 64, 128, 256), V: int = 128256, K: int = 4096) -> List[Dict]:
     """Generation log-probabilities (vocab 128256, K 4096), three variants timed in interleaved rounds:
     (a) the fused LM head + sampler as decode runs it, (b) its log-probability form
@@ -1843,6 +1909,7 @@ def main(argv=None) -> int:
                 "shard_shapes_tp8": lambda d: bench_shard_shapes(d, [n for n in SHARD_SHAPES if "tp8" in n]),
                 "shard_shapes_tp1": lambda d: bench_shard_shapes(d, [n for n in SHARD_SHAPES if "tp1" in n]),
                 "constrained_sample": bench_constrained_sample,
+                "penalty_sample": bench_penalty_sample,
                 "lm_head_sample_logprob": bench_lm_head_sample_logprob,
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),

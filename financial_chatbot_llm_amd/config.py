@@ -172,6 +172,10 @@ class EngineConfig:
     # constrained tool-call decoding (agent.automaton): capacity of the device automaton tables
     # (allocated at the first constrained request; ~64 MiB of token masks at V = 128256)
     fsm_max_states: int = 4096
+    # repetition / presence / frequency penalties (ops.penalty): sequences that may be penalised at
+    # once -- rows of the device count table, allocated at the first penalised request (2 bytes per
+    # token and slot: 16.4 MB at V = 128256); further penalised requests queue for a slot
+    penalty_slots: int = 64
 
     @classmethod
     def from_env(cls, **overrides) -> "EngineConfig":
@@ -208,6 +212,7 @@ class EngineConfig:
             use_cuda_graph=_env_bool("PENNY_HIPGRAPH", True),
             device=_env("PENNY_DEVICE", cls.device),
             fsm_max_states=_env_int("PENNY_FSM_MAX_STATES", cls.fsm_max_states),
+            penalty_slots=_env_int("PENNY_PENALTY_SLOTS", cls.penalty_slots),
         )
         return dataclasses.replace(c, **overrides)
 
@@ -262,6 +267,18 @@ class ServingConfig:
     # decide_low_confidence below the threshold); off by default
     decide_logprobs: bool = False
     decide_confidence_threshold: float = 0.5
+    # penalties of the streamed respond call (SamplingParams; neutral by default).  The decide call
+    # never gets them: its output is JSON
+    respond_repetition_penalty: float = 1.0
+    respond_presence_penalty: float = 0.0
+    respond_frequency_penalty: float = 0.0
+
+    def respond_penalties(self) -> dict:
+        """The respond call's penalty keyword arguments: only those off their neutral value."""
+        vals = {"repetition_penalty": (self.respond_repetition_penalty, 1.0),
+                "presence_penalty": (self.respond_presence_penalty, 0.0),
+                "frequency_penalty": (self.respond_frequency_penalty, 0.0)}
+        return {k: float(v) for k, (v, neutral) in vals.items() if float(v) != neutral}
 
     @classmethod
     def from_env(cls, **overrides) -> "ServingConfig":
@@ -277,6 +294,9 @@ class ServingConfig:
             constrain_toolcalls=_env_bool("PENNY_CONSTRAIN_TOOLCALLS", False),
             decide_logprobs=_env_bool("PENNY_DECIDE_LOGPROBS", False),
             decide_confidence_threshold=float(_env("PENNY_DECIDE_CONFIDENCE_THRESHOLD", "0.5")),
+            respond_repetition_penalty=_env_float("PENNY_RESPOND_REPETITION_PENALTY", cls.respond_repetition_penalty),
+            respond_presence_penalty=_env_float("PENNY_RESPOND_PRESENCE_PENALTY", cls.respond_presence_penalty),
+            respond_frequency_penalty=_env_float("PENNY_RESPOND_FREQUENCY_PENALTY", cls.respond_frequency_penalty),
         )
         return dataclasses.replace(c, **overrides)
 

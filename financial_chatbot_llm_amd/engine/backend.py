@@ -61,6 +61,7 @@ class EngineLLM(LLMBackend):
         self.constrain_tools = bool(constrain_tools) and self._can_constrain()
         self.fsm_max_states = fsm_max_states
         self._logprobs_ok: Optional[bool] = None     # decided (and warned about) at the first request
+        self._penalties_ok: Optional[bool] = None    # likewise
         self.respond_ignore_eos = respond_ignore_eos
         self.respond_tokens = respond_tokens
         self.stream_chunk_tokens = max(1, stream_chunk_tokens)
@@ -118,6 +119,31 @@ class EngineLLM(LLMBackend):
             self._logprobs_ok = not refused
         return self._logprobs_ok
 
+    def _parallel_engine(self) -> bool:
+        core = getattr(self.engine, "engine", None)
+        cfg = getattr(core, "cfg", None) or getattr(self.engine, "cfg", None)
+        ps = getattr(core, "ps", None)
+        return bool(getattr(cfg, "tp_size", 1) > 1 or getattr(cfg, "cp_size", 1) > 1
+                    or getattr(ps, "tp_size", 1) > 1 or getattr(getattr(core, "model", None), "tp_size", 1) > 1
+                    or getattr(core, "cp", None) is not None)
+
+    def _penalties(self, kw) -> dict:
+        """The repetition_penalty / presence_penalty / frequency_penalty keyword arguments of a call as
+        ``SamplingParams`` fields.  ``LLMEngine.add_request`` refuses penalised requests under TP /
+        CP; there they are dropped with one warning."""
+        pen = {k: float(kw[k]) for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")
+               if kw.get(k) is not None}
+        if not pen or (pen.get("repetition_penalty", 1.0) == 1.0 and not pen.get("presence_penalty")
+                       and not pen.get("frequency_penalty")):
+            return pen
+        if self._penalties_ok is None:
+            self._penalties_ok = not self._parallel_engine()
+            if not self._penalties_ok:
+                from ..utils.logging import get_logger
+                get_logger(__name__).warning("repetition / presence / frequency penalties need a TP = 1 engine "
+                                             "without CP; requests decode without them")
+        return pen if self._penalties_ok else {}
+
     def _constraint(self, tools):
         if not self.constrain_tools or not tools or self.decide_script is not None:
             return None
@@ -162,7 +188,7 @@ class EngineLLM(LLMBackend):
                                 forced_jump=jump, grammar=grammar, constraint=self._constraint(tools),
                                 ephemeral_kv=bool(kw.get("ephemeral_kv")),
                                 prompt_lookup=self.prompt_lookup, priority_ts=TURN_START.get(),
-                                logprobs=bool(kw.get("logprobs")) and self._can_logprob())
+                                logprobs=bool(kw.get("logprobs")) and self._can_logprob(), **self._penalties(kw))
         out = await self.engine.generate_all(ids, params)
         self._account(kw.get("purpose", "decide"), len(ids), out.seq)
         text = self.tok.decode(out.seq.output_ids)
@@ -174,7 +200,8 @@ class EngineLLM(LLMBackend):
         n = self.respond_tokens or max_tokens
         ids = self._encode(messages, None, n)
         params = SamplingParams(temperature=temperature, max_tokens=n, ignore_eos=self.respond_ignore_eos,
-                                ephemeral_kv=bool(kw.get("ephemeral_kv")), priority_ts=TURN_START.get())
+                                ephemeral_kv=bool(kw.get("ephemeral_kv")), priority_ts=TURN_START.get(),
+                                **self._penalties(kw))
         detok = IncrementalDetokenizer(self.tok)
         buf, k = [], 0
         async for o in self.engine.generate(ids, params):

@@ -8,7 +8,9 @@ other ranks).  Decode-size TP all-reduces take the custom one-shot xGMI kernel b
 """
 from __future__ import annotations
 
+import math
 import time
+from collections import deque
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence as Seq, Tuple
 
@@ -25,8 +27,8 @@ from ..utils.logging import get_logger
 from ..utils.metrics import METRICS
 from ..utils.profiling import StepProfiler, marker
 from .block_manager import make_block_manager
-from .model_runner import (CollectiveTimeout, ModelRunner, StepInputs, build_step_inputs, prefill_step_inputs,
-                           sample_rows)
+from .model_runner import (CollectiveTimeout, ModelRunner, StepInputs, build_step_inputs, penalised,
+                           prefill_step_inputs, sample_rows)
 from .scheduler import Scheduler, StepCostModel
 from .sequence import PENDING, SamplingParams, Sequence, SeqStatus
 from .speculative import PromptLookup, accept_draft
@@ -138,6 +140,12 @@ class LLMEngine:
                                   use_graphs=cfg.use_cuda_graph, graph_sizes=cfg.graph_batch_sizes,
                                   fsm_max_states=getattr(cfg, "fsm_max_states", 4096))
         self.requests: Dict[str, Sequence] = {}
+        # penalised requests hold a row of the runner's count table from add_request until they finish
+        # or are aborted (preemption keeps it: recompute keeps the tokens); with none free they wait
+        # here, in arrival order, and enter the scheduler when a slot is released
+        self.penalty_slots = max(1, int(getattr(cfg, "penalty_slots", 64)))
+        self._pen_free: Optional[List[int]] = None        # allocated with the table
+        self._pen_queue: deque = deque()
         self.timing = {"prepare_s": 0.0, "execute_s": 0.0, "post_s": 0.0}   # host-side step anatomy
         self.spec_stats = {"proposed": 0, "accepted": 0}   # prompt-lookup draft tokens
         self.scored_tokens = 0     # prompt tokens given a log-probability by score()
@@ -189,6 +197,25 @@ class LLMEngine:
         if params.logprobs and (self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None):
             raise NotImplementedError("generation log-probabilities: TP / CP engines sample vocabulary-parallel "
                                       "[B, 2] pairs, which do not carry them yet")
+        pens = (params.repetition_penalty, params.presence_penalty, params.frequency_penalty)
+        if not all(math.isfinite(float(x)) for x in pens):
+            raise ValueError(f"non-finite penalty {pens}")
+        if params.repetition_penalty <= 0:
+            raise ValueError(f"repetition_penalty must be > 0, got {params.repetition_penalty}")
+        if penalised(params):
+            if self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None:
+                raise NotImplementedError("penalties: TP / CP engines do not carry token-count tables yet")
+            if params.max_tokens > 32767:
+                raise ValueError(f"a penalised request counts at most 32767 output tokens, max_tokens = "
+                                 f"{params.max_tokens}")
+            self.requests[request_id] = seq
+            if not self._pen_take(seq):
+                if seq.num_tokens >= self.cfg.max_model_len:     # what scheduler.add would refuse later
+                    del self.requests[request_id]
+                    raise ValueError(f"prompt of {seq.num_tokens} tokens exceeds max_model_len "
+                                     f"{self.cfg.max_model_len}")
+                self._pen_queue.append(seq)                      # enters the scheduler with a slot
+                return seq
         self.requests[request_id] = seq
         if self.cp is not None and self.cp.wants(seq):
             self.cp.queue.append(seq)          # prefilled context-parallel before the next step
@@ -199,11 +226,49 @@ class LLMEngine:
     def abort(self, request_id: str) -> None:
         seq = self.requests.pop(request_id, None)
         if seq is not None and not seq.finished:
-            self.scheduler.abort(seq)
+            if seq in self._pen_queue:          # still waiting for a slot: the scheduler never saw it
+                self._pen_queue.remove(seq)
+                seq.status = SeqStatus.FINISHED
+            else:
+                self.scheduler.abort(seq)
             seq.finish_reason = "abort"
+            self._pen_release(seq)
 
     def has_work(self) -> bool:
-        return self.scheduler.has_work() or self._inflight is not None or bool(self.cp and self.cp.busy())
+        return (self.scheduler.has_work() or self._inflight is not None or bool(self.cp and self.cp.busy())
+                or bool(self._pen_queue))
+
+    # -- penalty slots -----------------------------------------------------------------------------
+    def _pen_take(self, seq: Sequence) -> bool:
+        """Give ``seq`` a free row of the count table, reset to its prompt.  The reset is enqueued on
+        the stream the steps run on, so it follows every earlier step that read the row."""
+        from ..ops import penalty
+        table = self.runner.ensure_penalty_table(self.penalty_slots)
+        if self._pen_free is None:
+            self._pen_free = list(range(self.penalty_slots - 1, -1, -1))
+        if not self._pen_free:
+            return False
+        seq.pen_slot, seq.pen_held, seq.pen_counted = self._pen_free.pop(), True, 0
+        penalty.reset(table, seq.pen_slot, seq.prompt_ids)
+        return True
+
+    def _pen_release(self, seq: Sequence, count_rest: bool = False) -> None:
+        """A finished (``count_rest``: its last tokens, which no later sample needed, are counted so the
+        row holds the whole output) or aborted sequence gives its slot back; the row's contents stand
+        until the slot is taken again.  The longest-waiting queued request takes it."""
+        if not seq.pen_held:
+            return
+        if count_rest:
+            from ..ops import penalty
+            rest = [(seq.pen_slot, t) for t in seq.output_ids[seq.pen_counted:] if t >= 0]
+            penalty.add(self.runner.pen_table, np.asarray(rest, np.int32).reshape(-1, 2))
+            seq.pen_counted = len(seq.output_ids)
+        seq.pen_held = False
+        self._pen_free.append(seq.pen_slot)
+        while self._pen_queue and self._pen_free:
+            nxt = self._pen_queue.popleft()
+            self._pen_take(nxt)
+            self.scheduler.add(nxt)
 
     def warmup(self) -> None:
         """Capture decode graphs (all TP ranks must call this together)."""
@@ -242,6 +307,7 @@ class LLMEngine:
                 self.scheduler.abort(seq)
                 seq.finish_reason = "error"
         self.requests.clear()
+        self._pen_queue.clear()
         if self.ps.tp_size > 1 and self.ps.is_tp_leader:
             comm.broadcast_step(StepInputs.control(StepInputs.CTRL_RCCL_FALLBACK))
         comm.fallback_to_rccl(str(e))
@@ -335,6 +401,8 @@ class LLMEngine:
         model's own stop token then arrives as the bonus sample and ends the sequence as usual)."""
         p = seq.params
         if p.prompt_lookup <= 0 or seq.finished:
+            return []
+        if seq.pen_slot >= 0:        # penalised: each verification row would need counts of its own
             return []
         k = len(seq.output_ids) + len(after)
         room = min(p.prompt_lookup, MAX_DRAFT, p.max_tokens - k - 1, self.cfg.max_model_len - seq.num_tokens - len(after) - 2)
@@ -554,6 +622,7 @@ class LLMEngine:
                 # reuse is by a LATER step, ordered after it on the stream
                 self.scheduler.finish(seq, reason)
                 self.requests.pop(seq.request_id, None)
+                self._pen_release(seq, count_rest=True)
             elif was_sampled:
                 self._stage_grammar(seq)    # used by the next launch (overrides its sample)
                 if sat_out and not seq.jump_queue and seq.status == SeqStatus.RUNNING:
@@ -670,6 +739,7 @@ class LLMEngine:
             if reason is not None:
                 self.scheduler.finish(seq, reason)
                 self.requests.pop(seq.request_id, None)
+                self._pen_release(seq, count_rest=True)
             else:
                 draft = self._propose(seq)
                 if draft:
@@ -790,6 +860,9 @@ class LLMEngine:
                 "constrained_tokens": self.runner.stats["constrained_tokens"],
                 "constrained_steps": self.runner.stats["constrained_steps"],
                 "logprob_steps": self.runner.stats["logprob_steps"],
+                "penalty_steps": self.runner.stats["penalty_steps"],
+                "penalty_rows": self.runner.stats["penalty_rows"],
+                "penalty_waiting": len(self._pen_queue),
                 "kv_dtype": self.kv.kv_dtype,
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),

@@ -65,6 +65,14 @@ class StepInputs:
     # log-probability form of whatever path it takes and every row's value rides back with the ids
     # (rows that did not ask discard theirs).  Not on the C4 wire: TP / CP engines refuse the request.
     want_logprobs: bool = False
+    # penalties (ops.penalty; None: no sampled row is penalised).  pen [S, 2] int32: the row's slot of
+    # the count table (-1: not penalised) and the row of the previous step's sampled vector that holds
+    # its still-pending previous token (-1: that token is counted already); pen_params [S, 3] f32:
+    # repetition, presence, frequency; pen_add [n, 2] int32: (slot, token) pairs counted before the
+    # step's rows read the table.  Not on the C4 wire: TP / CP engines refuse the request.
+    pen: Optional[np.ndarray] = None
+    pen_params: Optional[np.ndarray] = None
+    pen_add: Optional[np.ndarray] = None
 
     @property
     def num_prefill_tokens(self) -> int:
@@ -73,6 +81,7 @@ class StepInputs:
     # -- C4 wire format: one flat byte buffer (no pickling) ------------------------------------
     _ARRAYS = ("ids", "positions", "slots", "cu_q", "ctx_p", "bt_p", "ctx_d", "bt_d", "logits_idx", "temps",
                "seeds", "top_k", "top_p", "src", "pwork", "fsm_state")
+    _LOCAL = ("pen", "pen_params", "pen_add")     # staged with the step's arrays, never sent
 
     def pack(self) -> np.ndarray:
         """[header int64: max_q_len, then (dtype code, rows, cols) per array] + raw array bytes."""
@@ -150,6 +159,49 @@ def fsm_code(seq, k: int) -> int:
     return seq.fsm_off + s if s >= 0 else -1
 
 
+def penalised(params) -> bool:
+    """Does a request with these ``SamplingParams`` sample under penalties?  Any of the three off its
+    neutral value; scripted outputs sample nothing and ignore them."""
+    return params.forced_output is None and (params.repetition_penalty != 1.0 or params.presence_penalty != 0.0
+                                             or params.frequency_penalty != 0.0)
+
+
+class _PenRows:
+    """The penalty columns of a step under construction (``StepInputs.pen*``)."""
+
+    def __init__(self):
+        self.rows: List[Tuple[int, int]] = []
+        self.params: List[Tuple[float, float, float]] = []
+        self.adds: List[Tuple[int, int]] = []
+        self.any = False
+
+    def row(self, seq, k: int) -> None:
+        """The row that samples output token k of ``seq``: count the known tokens the table lacks
+        (``output_ids[pen_counted : first PENDING]``) and name a PENDING predecessor's device row."""
+        slot = seq.pen_slot
+        if slot < 0:
+            self.rows.append((-1, -1))
+            self.params.append((1.0, 0.0, 0.0))
+            return
+        self.any = True
+        out = seq.output_ids
+        i = seq.pen_counted
+        while i < k and out[i] >= 0:
+            self.adds.append((slot, out[i]))
+            i += 1
+        seq.pen_counted = i
+        pend = seq.pending_src if (i < k and out[i] < 0) else -1
+        p = seq.params
+        self.rows.append((slot, pend))
+        self.params.append((p.repetition_penalty, p.presence_penalty, p.frequency_penalty))
+
+    def arrays(self):
+        if not self.any:
+            return None, None, None
+        return (np.asarray(self.rows, np.int32).reshape(-1, 2), np.asarray(self.params, np.float32).reshape(-1, 3),
+                np.asarray(self.adds, np.int32).reshape(-1, 2))
+
+
 def _table(rows: List[List[int]]) -> np.ndarray:
     """Ragged block tables -> zero-padded [len(rows), max len] int32, in one vectorised scatter."""
     lens = np.fromiter((len(r) for r in rows), np.int64, len(rows))
@@ -172,6 +224,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     ctx_p, tables_p = [], []
     logits_idx, temps, seeds, tk, tp, fsm = [], [], [], [], [], []
     want_lp = False
+    pen = _PenRows()
     max_q = 0
     for seq, start, n in batch.prefill:
         np_ = len(seq.prompt_ids)
@@ -199,6 +252,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
                 tk.append(seq.params.top_k)
                 tp.append(seq.params.top_p)
                 fsm.append(fsm_code(seq, k0 + i))
+                pen.row(seq, k0 + i)
     Tp = cu[-1]
     ids_d, pos_d, slots_d = [], [], []
     ctx_d, tables_d, src = [], [], []
@@ -220,6 +274,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
         tk.append(seq.params.top_k)
         tp.append(seq.params.top_p)
         fsm.append(fsm_code(seq, len(seq.output_ids)))
+        pen.row(seq, len(seq.output_ids))
         want_lp = want_lp or seq.params.logprobs
 
     i32 = lambda x: np.asarray(x, np.int32)  # noqa: E731
@@ -232,7 +287,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     return StepInputs(cat(ids_parts, ids_d), cat(pos_parts, pos_d), cat(slot_parts, slots_d), i32(cu), i32(ctx_p),
                       _table(tables_p), max_q, i32(ctx_d), bt_d, np.asarray(logits_idx, np.int64),
                       np.asarray(temps, np.float32), np.asarray(seeds, np.int64), i32(tk), np.asarray(tp, np.float32),
-                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None, bool(want_lp))
+                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None, bool(want_lp), *pen.arrays())
 
 
 def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
@@ -315,12 +370,15 @@ class _DecodeGraph:
 # Which sampler a step runs, and which captured graph holds it, decided from booleans alone.  Samplers:
 # "fsm" logits -> masked threshold -> masked sampler + automaton state update, "shard" the TP
 # vocabulary-parallel sampler, "fused" inside the LM head (no logits, no top-k / top-p), "logits"
-# logits -> threshold -> sampler.
-def sampler_kind(fsm: bool, filters: bool, shard: bool, fused: bool) -> str:
-    """Sampler of an eager step: constrained rows, else the shard / fused LM-head sampler where the
-    model has one and no row carries top-k / top-p, else the logits sampler."""
+# logits -> threshold -> sampler, "pen" logits -> penalties -> threshold -> sampler.
+def sampler_kind(fsm: bool, filters: bool, shard: bool, fused: bool, pen: bool = False) -> str:
+    """Sampler of an eager step: constrained rows, else penalised rows, else the shard / fused LM-head
+    sampler where the model has one and no row carries top-k / top-p, else the logits sampler.  A step
+    with constrained AND penalised rows is "fsm": the penalties run on its logits first."""
     if fsm:
         return "fsm"
+    if pen:
+        return "pen"
     if not filters and (shard or fused):
         return "shard" if shard else "fused"
     return "logits"
@@ -335,16 +393,17 @@ def default_graph_kind(shard: bool, fused: bool) -> str:
 DEFAULT_GRAPH, EAGER = "default", "eager"
 
 
-def graph_plan(fsm: bool, filters: bool, lp: bool, bucket_fused: bool, tp: bool):
+def graph_plan(fsm: bool, filters: bool, lp: bool, bucket_fused: bool, tp: bool, pen: bool = False):
     """What runs a pure-decode step whose bucket's default graph is ``bucket_fused`` or not:
     DEFAULT_GRAPH, EAGER, or the (sampler, lp) of the bucket's twin graph, captured on the first step
-    that needs it.  The default graph has no automaton, no log-probabilities and, when fused, no
-    top-k / top-p; twins exist at TP = 1 only."""
-    if not (fsm or lp or (filters and bucket_fused)):
+    that needs it.  The default graph has no automaton, no penalties, no log-probabilities and, when
+    fused, no top-k / top-p; twins exist at TP = 1 only, and none holds penalties and the automaton
+    together (such a step runs eagerly)."""
+    if not (fsm or pen or lp or (filters and bucket_fused)):
         return DEFAULT_GRAPH
-    if tp:
+    if tp or (fsm and pen):
         return EAGER
-    return ("fsm" if fsm else "logits" if filters or not bucket_fused else "fused"), lp
+    return ("fsm" if fsm else "pen" if pen else "logits" if filters or not bucket_fused else "fused"), lp
 
 
 class ModelRunner:
@@ -383,12 +442,17 @@ class ModelRunner:
         self._fsm_known: Dict[str, int] = {}              # automaton key -> state offset
         self._fsm_tok_key = None
         self.last_fsm_state: Optional[torch.Tensor] = None   # state_out of the latest step, beside last_sampled
+        # penalties (ops.penalty): the count table, allocated by the engine at the first penalised
+        # request (``ensure_penalty_table``), and the static inputs of the "pen" graph twins
+        self.pen_table: Optional[ops.PenaltyTable] = None
+        self._pen_static = None
         self._static = None
         self.graph_pool = None
         self.stats = {"steps": 0, "graph_steps": 0, "tokens": 0, "prefill_steps": 0, "prefill_step_tokens": 0,
                       "prefill_tile_pad_rows": 0, "prefill_m_hist": [0] * len(PREFILL_M_BUCKETS), "gpu_graph_s": 0.0, "gpu_eager_s": 0.0,
                       "gpu_idle_s": 0.0, "gpu_idle_gaps": 0, "_prev_end_ev": None, "overlap_steps": 0,
-                      "constrained_steps": 0, "constrained_tokens": 0, "logprob_steps": 0}
+                      "constrained_steps": 0, "constrained_tokens": 0, "logprob_steps": 0,
+                      "penalty_steps": 0, "penalty_rows": 0}
         # TP prefill steps of >= overlap_min_rows rows run as two micro-batches whose all-reduces
         # overlap the other half's compute (PENNY_TP_OVERLAP=0 disables)
         self.tp_overlap = os.environ.get("PENNY_TP_OVERLAP", "1") == "1"
@@ -432,7 +496,7 @@ class ModelRunner:
             return
         arrs = []
         total = 0
-        for name in StepInputs._ARRAYS:
+        for name in StepInputs._ARRAYS + StepInputs._LOCAL:
             a = getattr(si, name)
             if a is None or a.dtype not in self._STAGE_DTYPES:
                 continue
@@ -511,6 +575,35 @@ class ModelRunner:
         """Step-local automaton states: carry codes (<= -2) read the previous step's ``state_out``
         (``last_fsm_state``) -- before any kernel of this step writes it."""
         return torch.where(code <= -2, self.last_fsm_state[(-2 - code).clamp(min=0).long()], code)
+
+    def ensure_penalty_table(self, slots: int) -> "ops.PenaltyTable":
+        """The count table of the penalised sequences, allocated at the first call: its pointer is
+        captured by the "pen" graph twins, so it is never replaced."""
+        if self.pen_table is None:
+            self.pen_table = ops.PenaltyTable(slots, self.model.cfg.vocab_size, self.device)
+            logger.info(f"penalty table: {slots} slots x {self.pen_table.Vs} tokens "
+                        f"({self.pen_table.table.numel() * 2 / 1e6:.1f} MB)")
+        return self.pen_table
+
+    def _resolve_pending_tok(self, row: torch.Tensor) -> torch.Tensor:
+        """Pending rows (of the previous step's sampled vector, -1: none) -> the tokens they hold, read
+        from ``last_sampled`` before any kernel of this step writes it."""
+        return torch.where(row >= 0, self.last_sampled[row.clamp(min=0).long()], row)
+
+    def _pen_inputs(self, si: StepInputs):
+        """Count ``si.pen_add`` into the table and return the step's (slot, pending token, params
+        [3, S]) on the device -- at the point of the step where the pending ids are gathered."""
+        if self.pen_table is None:
+            raise RuntimeError("a penalised step without a penalty table")
+        if len(si.pen_add):
+            ops.penalty.add(self.pen_table, self._to_dev(si.pen_add))
+        pen = self._to_dev(si.pen)
+        return (pen[:, 0].contiguous(), self._resolve_pending_tok(pen[:, 1]),
+                self._to_dev(si.pen_params).t().contiguous())
+
+    def _count_penalty_step(self, si: StepInputs) -> None:
+        self.stats["penalty_steps"] += 1
+        self.stats["penalty_rows"] += int((si.pen[:, 0] >= 0).sum())
 
     def _gather_pending(self, ids: torch.Tensor, src: torch.Tensor, offset: int) -> None:
         """ids[offset + r] <- last_sampled[src[r]] where src[r] >= 0 (device-side, no host sync)."""
@@ -597,21 +690,23 @@ class ModelRunner:
         state = None
         if si.fsm_state is not None:       # resolved where the pending ids are gathered: before any write
             state = self._resolve_fsm(self._to_dev(si.fsm_state))
+        pen = self._pen_inputs(si) if si.pen is not None else None
         h = self._hidden(si)
         hs = h.index_select(0, self._to_dev(si.logits_idx))
         filt = self._has_filters(si)
-        kind = sampler_kind(state is not None, filt, self._shard_sampling(), self._fused_sampling(hs))
+        kind = sampler_kind(state is not None, filt, self._shard_sampling(), self._fused_sampling(hs),
+                            pen is not None)
         if kind == "shard":
             self.stats["vocab_parallel_sample_steps"] = self.stats.get("vocab_parallel_sample_steps", 0) + 1
         elif kind == "fused":
             self.stats["fused_lm_head_steps"] = self.stats.get("fused_lm_head_steps", 0) + 1
         return self._sample(hs, kind, self._to_dev(si.temps), self._to_dev(si.seeds),
                             self._to_dev(si.top_k) if filt else None, self._to_dev(si.top_p) if filt else None,
-                            state, si.want_logprobs)
+                            state, si.want_logprobs, pen)
 
     def _sample(self, hs: torch.Tensor, kind: str, temps: torch.Tensor, seeds: torch.Tensor,
                 top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
-                state: Optional[torch.Tensor] = None, lp: bool = False) -> Sampled:
+                state: Optional[torch.Tensor] = None, lp: bool = False, pen=None) -> Sampled:
         """The one sampling stage, of eager steps and captured graphs alike: one token per hidden row
         ``hs`` through the sampler ``kind`` (see ``sampler_kind``).  ``lp``: the log-probability form
         -- the same tokens, the fused LM head still without logits, a step that holds its logits
@@ -626,12 +721,21 @@ class ModelRunner:
             return Sampled(ops.lm_head_sample(hs, m.lm_weight(), temps, seeds, wt=self._lm_tiled()))
         logits = m.logits(hs).contiguous()
         state_out = None
+        chosen = logits                  # what the sampler reads: the penalised logits of a "pen" step
+        if pen is not None:
+            # penalties first (then the automaton mask, then top-k / top-p): in place, unless the step
+            # reports log-probabilities -- those stay the raw model distribution
+            slot, ptok, par = pen
+            chosen = ops.apply_penalties(logits, slot, ptok, par[0], par[1], par[2], self.pen_table,
+                                         out=torch.empty_like(logits) if lp else None)
+        elif kind == "pen":
+            raise RuntimeError("a penalised step without its penalty inputs")
         if kind == "fsm":
             if self.fsm is None:
                 raise RuntimeError("a constrained step without a registered automaton")
-            out, state_out = ops.sample_constrained(logits, temps, seeds, state, self.fsm, top_k=top_k, top_p=top_p)
+            out, state_out = ops.sample_constrained(chosen, temps, seeds, state, self.fsm, top_k=top_k, top_p=top_p)
         else:                       # device-side top-k / top-p threshold when given
-            out = ops.sample(logits, temps, seeds, top_k=top_k, top_p=top_p)
+            out = ops.sample(chosen, temps, seeds, top_k=top_k, top_p=top_p)
         return Sampled(out, state_out, ops.token_logprobs(logits, out) if lp else None)
 
     def execute(self, si: StepInputs) -> List[int]:
@@ -693,6 +797,8 @@ class ModelRunner:
         self.last_sampled[:n].copy_(out[:n].to(torch.int32), non_blocking=True)
         if si.want_logprobs:
             self.stats["logprob_steps"] += 1
+        if si.pen is not None:
+            self._count_penalty_step(si)
         if si.fsm_state is not None:
             self.last_fsm_state[:n].copy_(so[:n], non_blocking=True)
             self.stats["constrained_steps"] += 1
@@ -819,6 +925,11 @@ class ModelRunner:
         default sampler, decided here and returned)."""
         s = self._static
         fsm = kind == "fsm"
+        pen = None
+        if kind == "pen":     # pending rows -> tokens, before the sampler of this graph writes last_sampled
+            ps = self._pen_static
+            ps["tok"][:B].copy_(self._resolve_pending_tok(ps["i32"][1, :B]))
+            pen = (ps["i32"][0, :B], ps["tok"][:B], ps["f32"][:, :B])
         self._gather_pending(s["ids"], s["src"][:B], 0)
         if fsm:      # carry codes -> states, in place, before the sampler of this graph writes state_out
             s["fsm"][:B].copy_(self._resolve_fsm(s["fsm"][:B]))
@@ -837,9 +948,9 @@ class ModelRunner:
             kind = default_graph_kind(self._shard_sampling(), self._fused_sampling(h))
         # the top-k / top-p threshold kernel is always in a graph that samples from logits: unfiltered
         # rows (k=0, p=1) exit after reading their parameters; under TP such rows replay eagerly
-        filt = kind in ("fsm", "logits")
+        filt = kind in ("fsm", "logits", "pen")
         return kind, self._sample(h, kind, s["temps"][:B], s["seeds"][:B], s["top_k"][:B] if filt else None,
-                                  s["top_p"][:B] if filt else None, s["fsm"][:B] if fsm else None, lp)
+                                  s["top_p"][:B] if filt else None, s["fsm"][:B] if fsm else None, lp, pen)
 
     def _capture(self, B: int, kind: Optional[str] = None, lp: bool = False) -> _DecodeGraph:
         for _ in range(2):      # warm up (allocator + hipBLASLt heuristics) outside the capture
@@ -872,7 +983,7 @@ class ModelRunner:
         B = self._bucket(si.num_decode)
         G = self.graphs[B]
         plan = graph_plan(si.fsm_state is not None, self._has_filters(si), si.want_logprobs, G.fused,
-                          getattr(self.model, "tp_size", 1) > 1)
+                          getattr(self.model, "tp_size", 1) > 1, si.pen is not None)
         if plan == DEFAULT_GRAPH:
             return G
         if plan == EAGER:
@@ -897,6 +1008,8 @@ class ModelRunner:
         are restored after."""
         B, kind, lp = key
         s = self._static
+        if kind == "pen":
+            self._alloc_pen_static()       # no row penalised (slot -1) until the replay fills them in
         saved = (s["slots"][:B].clone(), s["src"][:B].clone(), s["fsm"][:B].clone())
         s["slots"][:B].fill_(-1)
         s["src"][:B].fill_(-1)
@@ -908,6 +1021,39 @@ class ModelRunner:
             s["src"][:B].copy_(saved[1])
             s["fsm"][:B].copy_(saved[2])
             torch.cuda.synchronize()
+
+    def _alloc_pen_static(self) -> None:
+        """Static inputs of the "pen" twins, allocated with the first of them (the default graphs and
+        their staging buffers stay as they are): slot | pending row [2, B] int32 and the parameters
+        [3, B] f32, each fed by one pinned copy per penalised graph step; ``tok`` holds the pending
+        tokens the graph resolves."""
+        B = self.max_decode_batch
+        if self._pen_static is None:
+            self._pen_static = {
+                "i32": torch.zeros((2, B), dtype=torch.int32, device=self.device),
+                "tok": torch.full((B,), -1, dtype=torch.int32, device=self.device),
+                "f32": torch.zeros((3, B), dtype=torch.float32, device=self.device),
+                "pinned": [(torch.zeros((2, B), dtype=torch.int32).pin_memory(),
+                            torch.zeros((3, B), dtype=torch.float32).pin_memory()) for _ in range(2)],
+                "flip": 0,
+            }
+        self._pen_static["i32"].fill_(-1)
+
+    def _stage_pen_static(self, si: StepInputs, B: int) -> None:
+        """The penalty inputs of a "pen" twin's replay; ``pen_add`` is counted eagerly in front of it."""
+        ps = self._pen_static
+        n = si.num_decode
+        if len(si.pen_add):
+            ops.penalty.add(self.pen_table, torch.from_numpy(si.pen_add).pin_memory().to(self.device, non_blocking=True))
+        pi, pf = ps["pinned"][ps["flip"]]
+        ps["flip"] ^= 1
+        a, f = pi.numpy(), pf.numpy()
+        a[:, :B] = -1
+        a[:, :n] = si.pen.T
+        f[:, :B] = np.asarray([[1.0], [0.0], [0.0]], np.float32)
+        f[:, :n] = si.pen_params.T
+        ps["i32"].copy_(pi, non_blocking=True)
+        ps["f32"].copy_(pf, non_blocking=True)
 
     def _bucket(self, n: int) -> int:
         for b in self.graph_sizes:
@@ -951,6 +1097,8 @@ class ModelRunner:
         s = self._static
         s["f32"].copy_(self._pinned_f, non_blocking=True)
         s["seeds"].copy_(self._pinned_l, non_blocking=True)
+        if si.pen is not None:             # only a "pen" twin is chosen for such a step (graph_plan)
+            self._stage_pen_static(si, B)
         G.graph.replay()
         self.stats["graph_steps"] += 1
         return Sampled(G.out[:n], G.state_out, G.logprob)

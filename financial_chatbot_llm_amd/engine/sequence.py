@@ -47,6 +47,16 @@ class SamplingParams:
     # temperature, top-k / top-p and the constraint choose the token, not the number.  Never changes a
     # token.  TP = 1 without CP only.
     logprobs: bool = False
+    # penalties on tokens the sequence holds already (ops.penalty), applied to the logits in front of
+    # the automaton mask, top-k / top-p and the sampler: repetition divides a positive (multiplies a
+    # negative) logit of every token in the prompt or the output; presence is subtracted once and
+    # frequency once per occurrence, for tokens of the output only.  Neutral: 1, 0, 0.  A scripted
+    # output (forced_output) ignores them; a penalised request proposes no prompt-lookup drafts and
+    # needs max_tokens <= 32767.  Reported log-probabilities stay the raw model distribution.
+    # TP = 1 without CP only.
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
 
 
 class SeqStatus(enum.Enum):
@@ -110,6 +120,12 @@ class Sequence:
         self.fsm_off: Optional[int] = None
         self.fsm_pos = 0
         self.fsm_state = 0
+        # penalties: pen_slot -- the sequence's row of the runner's count table (-1: not penalised; kept
+        # after the slot is released, whose contents stand until it is taken again); pen_held -- the
+        # slot is this sequence's; pen_counted -- output tokens [0, pen_counted) are in the table
+        self.pen_slot = -1
+        self.pen_held = False
+        self.pen_counted = 0
 
     def fsm_state_before(self, k: int) -> int:
         """Local automaton state in front of output token k (every earlier token known; -1: the

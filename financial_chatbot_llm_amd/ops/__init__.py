@@ -15,6 +15,8 @@ from .sampling import (apply_top_k_top_p, fused_lm_head_ok, fused_logprob_ok, lm
                        lm_head_stream_sample_logprob, merge_logprob_stats, pick_pairs, sample, sample_shard,
                        token_logprobs)
 from .constrain import FsmTables, build_masks, sample_constrained
+from . import penalty
+from .penalty import PenaltyTable, apply_penalties
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
            "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",

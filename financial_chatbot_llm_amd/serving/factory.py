@@ -32,7 +32,8 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
     retrieval = RetrievalService(embedder, store)
     llm = llm or StubLLM()
     if not serving.tools:
-        agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens)
+        agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
+                           respond_penalties=serving.respond_penalties())
     else:
         agent = LLMAgent(llm, make_retrieval_tool(retrieval),
                          extra_tools=[make_plot_tool()], temperature=serving.temperature,
@@ -40,7 +41,8 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
                          max_decide_tokens=serving.max_decide_tokens, max_tool_steps=max_tool_steps,
                          today_fn=today_fn, max_transaction_tokens=retrieval_limit_tokens(),
                          decide_logprobs=serving.decide_logprobs,
-                         decide_confidence_threshold=serving.decide_confidence_threshold)
+                         decide_confidence_threshold=serving.decide_confidence_threshold,
+                         respond_penalties=serving.respond_penalties())
     return Services(db=db, kafka=kafka, agent=agent, retrieval=retrieval, serving=serving)
 
 
@@ -66,14 +68,16 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
                     history_token_budget=serving.history_token_budget,
                     constrain_tools=serving.constrain_toolcalls, fsm_max_states=engine_cfg.fsm_max_states)
     if not serving.tools:
-        agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens)
+        agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
+                           respond_penalties=serving.respond_penalties())
     else:
         agent = LLMAgent(llm, make_retrieval_tool(retrieval), extra_tools=[make_plot_tool()],
                          temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
                          max_decide_tokens=serving.max_decide_tokens, max_tool_steps=max_tool_steps,
                          max_transaction_tokens=retrieval_cfg.max_limit_tokens,
                          decide_logprobs=serving.decide_logprobs,
-                         decide_confidence_threshold=serving.decide_confidence_threshold)
+                         decide_confidence_threshold=serving.decide_confidence_threshold,
+                         respond_penalties=serving.respond_penalties())
     return Services(db=db or Database(), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)
 

@@ -50,6 +50,12 @@ def parse(argv=None):
     ap.add_argument("--constrain-toolcalls", action="store_true",
                     default=os.environ.get("PENNY_CONSTRAIN_TOOLCALLS", "0").lower() in ("1", "true", "yes"),
                     help="decide calls sample under the tool-call token automaton (TP = 1 only)")
+    ap.add_argument("--respond-repetition-penalty", type=float, default=None,
+                    help="repetition penalty of the streamed respond call (PENNY_RESPOND_REPETITION_PENALTY; 1: off)")
+    ap.add_argument("--respond-presence-penalty", type=float, default=None,
+                    help="presence penalty of the respond call (PENNY_RESPOND_PRESENCE_PENALTY; 0: off)")
+    ap.add_argument("--respond-frequency-penalty", type=float, default=None,
+                    help="frequency penalty of the respond call (PENNY_RESPOND_FREQUENCY_PENALTY; 0: off)")
     ap.add_argument("--max-model-len", type=int, default=8192)
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default=os.environ.get("PENNY_KV_DTYPE", "bf16"),
                     help="KV pool element type (fp8: e4m3, twice the tokens in the same memory; TP = CP = 1)")
@@ -80,12 +86,15 @@ def build_leader_services(args, engine, device):
         embedder = HashEmbedder(768)
         store = NumpyVectorStore(768)
     retrieval = RetrievalService(embedder, store)
-    serving = config.ServingConfig.from_env()
+    flags = {f"respond_{k}_penalty": getattr(args, f"respond_{k}_penalty", None)
+             for k in ("repetition", "presence", "frequency")}
+    serving = config.ServingConfig.from_env(**{k: v for k, v in flags.items() if v is not None})
     llm = EngineLLM(engine, max_model_len=args.max_model_len, history_token_budget=serving.history_token_budget,
                     constrain_tools=args.constrain_toolcalls or serving.constrain_toolcalls,
                     fsm_max_states=config.EngineConfig.from_env().fsm_max_states)
     if args.no_tools or not serving.tools:
-        agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens)
+        agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
+                           respond_penalties=serving.respond_penalties())
     else:
         from .factory import retrieval_limit_tokens
         agent = LLMAgent(llm, make_retrieval_tool(retrieval), extra_tools=[make_plot_tool()],
@@ -93,7 +102,8 @@ def build_leader_services(args, engine, device):
                          max_decide_tokens=serving.max_decide_tokens, max_tool_steps=args.tool_steps,
                          max_transaction_tokens=retrieval_limit_tokens(),     # PENNY_MAX_TRANSACTION_TOKENS
                          decide_logprobs=args.decide_logprobs or serving.decide_logprobs,
-                         decide_confidence_threshold=serving.decide_confidence_threshold)
+                         decide_confidence_threshold=serving.decide_confidence_threshold,
+                         respond_penalties=serving.respond_penalties())
     broker = InMemoryBroker() if args.smoke else None
     return Services(db=Database(uri="" if args.smoke else None), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)
