@@ -61,7 +61,7 @@ class LLMAgent:
                  system_prompt: Optional[str] = None, tool_prompt: Optional[str] = None,
                  max_transaction_tokens: Optional[int] = config.MAX_TRANSACTION_TOKENS,
                  decide_logprobs: bool = False, decide_confidence_threshold: float = 0.5,
-                 respond_penalties: Optional[Dict[str, float]] = None):
+                 decide_top_logprobs: int = 0, respond_penalties: Optional[Dict[str, float]] = None):
         self.llm = llm
         # repetition_penalty / presence_penalty / frequency_penalty of the streamed respond call
         # (ServingConfig.respond_penalties); the decide call never gets them: its output is JSON
@@ -70,6 +70,10 @@ class LLMAgent:
         # tokens' log-probabilities and exp(mean) goes to the metrics registry
         self.decide_logprobs = bool(decide_logprobs)
         self.decide_confidence_threshold = float(decide_confidence_threshold)
+        # decide margin (ServingConfig.decide_top_logprobs): the decide call asks for N >= 2 alternatives
+        # per sampled token; the first sampled token's log-probability minus the best OTHER alternative's
+        # goes to the metrics registry -- how close the two-way routing choice was
+        self.decide_top_logprobs = max(2, int(decide_top_logprobs)) if int(decide_top_logprobs) > 0 else 0
         self.retrieval_tool = retrieval_tool
         self.tools: Dict[str, Tool] = {retrieval_tool.name: retrieval_tool}
         for t in extra_tools:
@@ -144,10 +148,13 @@ class LLMAgent:
     async def _decide_retrieval_node(self, state: AgentState) -> AgentState:
         logger.info("Deciding if transaction retrieval is needed")
         extra = {"logprobs": True} if self.decide_logprobs else {}
+        if self.decide_top_logprobs:
+            extra["top_logprobs"] = self.decide_top_logprobs
         result = await self.llm.agenerate(self.decide_messages(state), tools=self.bound_tools,
                                           temperature=self.temperature, max_tokens=self.max_decide_tokens,
                                           purpose="decide", ephemeral_kv=bool(state["tool_results"]), **extra)
         self._record_confidence(result)
+        self._record_margin(result)
         logger.info(f"Decide Retrieval Response: {result.text!r} tool_calls={[t.to_dict() for t in result.tool_calls]}")
         if result.tool_calls:
             tc = result.tool_calls[0]  # only the first call is honoured (llm_agent.py:100)
@@ -171,6 +178,28 @@ class LLMAgent:
         if conf < self.decide_confidence_threshold:
             METRICS.inc("decide_low_confidence")
         logger.debug(f"decide confidence {conf:.4f} (mean logprob {mean:.4f})")
+
+    def _record_margin(self, result) -> None:
+        """The first sampled token of the decide call against its best other alternative: log p(token)
+        minus the largest log-probability among the listed tokens that are not it (negative when the
+        sampler drew a less likely token).  A decide that sampled nothing (scripted) records nothing."""
+        tops = getattr(result, "top_logprobs", None)
+        lps = getattr(result, "logprobs", None)
+        toks = getattr(result, "token_ids", None)
+        if not self.decide_top_logprobs or not tops or not lps or not toks:
+            return
+        k = next((i for i, t in enumerate(tops) if t), None)
+        if k is None or k >= len(lps) or k >= len(toks) or lps[k] is None:
+            return
+        lp = float(lps[k])
+        others = [v for i, v in tops[k] if i != toks[k]]
+        if not others or lp != lp:
+            return
+        from ..utils.metrics import METRICS
+        margin = lp - max(others)
+        METRICS.inc("decide_margin_sum", margin)
+        METRICS.inc("decide_margin_count")
+        logger.debug(f"decide margin {margin:.4f} nats; first sampled token's alternatives {list(tops[k])}")
 
     async def _retrieve_data_node(self, state: AgentState) -> AgentState:
         logger.info("Retrieving transaction data")

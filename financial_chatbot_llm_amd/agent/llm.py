@@ -35,6 +35,12 @@ class LLMResult:
     # over the entries that carry one (None when none does)
     logprobs: Optional[List[Optional[float]]] = None
     mean_logprob: Optional[float] = None
+    # agenerate(..., top_logprobs=N): per generated token, the N most likely tokens of the same raw
+    # distribution as (token id, log-probability) pairs, most likely first (None: the token was not
+    # sampled); None when not requested or not available
+    top_logprobs: Optional[List[Optional[List[tuple]]]] = None
+    # the generated token ids, parallel to logprobs / top_logprobs (None: the backend reports none)
+    token_ids: Optional[List[int]] = None
 
 
 def mean_logprob(logprobs: Optional[Sequence[Optional[float]]]) -> Optional[float]:

@@ -865,6 +865,65 @@ def bench_lm_head_sample_logprob(dev, Ms=(16, 64, 128, 256), V: int = 128256, K:
     return out
 
 
+def bench_topn_logprob(dev, Ms=(16, 64, 128, 256), Ns=(1, 5, 20), V: int = 128256, K: int = 4096) -> List[Dict]:
+    """Top-N alternatives (vocab 128256, bf16 logits), per (M rows, N per row) in interleaved rounds:
+    the kernel pair -- ops.token_logprobs alone against ops.topn_logprobs on the same logits -- and the
+    step pair -- the fused LM head in its log-probability form (what a logprobs=True decode step runs)
+    against the same followed by the LM-head logits GEMM and ops.topn_logprobs (what that step runs once
+    a row asks for alternatives).  step_price = the second pair's difference.  Each figure is the median
+    of 9 rounds of 50 calls, with the rounds' min and max as the run-to-run spread."""
+    from ..ops import gemm
+    gemm.load_gemm_tuning("llama3-8b")
+    out = []
+    w = torch.randn((V, K), device=dev).to(torch.bfloat16) * 0.02
+    wt = gemm.tile_weight(w)
+
+    def timed(fns, rounds=9, iters=50):
+        for f in fns.values():
+            f()
+        torch.cuda.synchronize()
+        res = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, f in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    f()
+                b.record()
+                b.synchronize()
+                res[k].append(a.elapsed_time(b) * 1e3 / iters)
+        return {k: (statistics.median(v), min(v), max(v)) for k, v in res.items()}
+    for M in Ms:
+        x = torch.randn((M, K), device=dev).to(torch.bfloat16)
+        temps = torch.full((M,), 0.7, device=dev)
+        sd = torch.arange(M, dtype=torch.int64, device=dev) * 977
+        logits = gemm.linear(x, w).contiguous()
+        ids = ops.sample(logits, temps, sd)
+        lp = torch.empty((M,), dtype=torch.float32, device=dev)
+        bufs = (lp, torch.empty((M, ops.sampling.TOPN_MAX), dtype=torch.int32, device=dev),
+                torch.empty((M, ops.sampling.TOPN_MAX), dtype=torch.float32, device=dev))
+        tiled = wt if M < ops.sampling.FUSED_LM_HEAD_MIN_M else None
+        for n in Ns:
+            tn = torch.full((M,), n, dtype=torch.int32, device=dev)
+
+            def step_topn():
+                tok, own = ops.lm_head_sample_logprob(x, w, temps, sd, wt=tiled)
+                ops.topn_logprobs(gemm.linear(x, w), tok, tn, out=(own, bufs[1], bufs[2]))
+            r = timed({"token_logprobs": lambda: ops.token_logprobs(logits, ids, out=lp),
+                       "topn_logprobs": lambda: ops.topn_logprobs(logits, ids, tn, out=bufs),
+                       "fused_lp": lambda: ops.lm_head_sample_logprob(x, w, temps, sd, wt=tiled),
+                       "fused_lp_gemm_topn": step_topn})
+            row = {"op": "topn_logprob", "M": M, "N": n, "V": V, "K": K}
+            for k, (med, lo, hi) in r.items():
+                row[k + "_us"] = round(med, 1)
+                row[k + "_spread_us"] = [round(lo, 1), round(hi, 1)]
+            row["kernel_price_us"] = round(r["topn_logprobs"][0] - r["token_logprobs"][0], 1)
+            row["step_price_us"] = round(r["fused_lp_gemm_topn"][0] - r["fused_lp"][0], 1)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+    return out
+
+
 def bench_bge_query(dev) -> List[Dict]:
     """bge-base encoder latency on retrieval-size query batches (the per-turn critical path): the
     four projections on hipBLASLt (+ the GELU pass) vs the tile kernel with the bias / bias+GELU
@@ -1911,6 +1970,7 @@ def main(argv=None) -> int:
                 "constrained_sample": bench_constrained_sample,
                 "penalty_sample": bench_penalty_sample,
                 "lm_head_sample_logprob": bench_lm_head_sample_logprob,
+                "topn_logprob": bench_topn_logprob,
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),

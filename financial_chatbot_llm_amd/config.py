@@ -267,6 +267,10 @@ class ServingConfig:
     # decide_low_confidence below the threshold); off by default
     decide_logprobs: bool = False
     decide_confidence_threshold: float = 0.5
+    # the decide call also asks for this many alternatives per sampled token (SamplingParams.top_logprobs;
+    # at least 2 when on) and records the first sampled token's margin over its best other alternative
+    # (decide_margin_sum / _count); 0: off
+    decide_top_logprobs: int = 0
     # penalties of the streamed respond call (SamplingParams; neutral by default).  The decide call
     # never gets them: its output is JSON
     respond_repetition_penalty: float = 1.0
@@ -294,6 +298,7 @@ class ServingConfig:
             constrain_toolcalls=_env_bool("PENNY_CONSTRAIN_TOOLCALLS", False),
             decide_logprobs=_env_bool("PENNY_DECIDE_LOGPROBS", False),
             decide_confidence_threshold=float(_env("PENNY_DECIDE_CONFIDENCE_THRESHOLD", "0.5")),
+            decide_top_logprobs=_env_int("PENNY_DECIDE_TOP_LOGPROBS", cls.decide_top_logprobs),
             respond_repetition_penalty=_env_float("PENNY_RESPOND_REPETITION_PENALTY", cls.respond_repetition_penalty),
             respond_presence_penalty=_env_float("PENNY_RESPOND_PRESENCE_PENALTY", cls.respond_presence_penalty),
             respond_frequency_penalty=_env_float("PENNY_RESPOND_FREQUENCY_PENALTY", cls.respond_frequency_penalty),

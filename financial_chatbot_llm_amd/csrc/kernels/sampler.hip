@@ -500,14 +500,15 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os
   m = nm;
 }
 
+// The row's (max, sum exp): lse_thread leaves each thread's own pair over its chunks, lse_waves the 16
+// per-wave partials in sm / ss (thread 0 keeps wave 0's in m, s), lse_finish merges them on thread 0:
+// one code path, one order, for every kernel that reports a log-probability off a logits row -- their
+// values for the same row and id are bit-equal.
 template <typename T>
-__global__ void __launch_bounds__(1024) token_logprob_kernel(const T* __restrict__ logits, long row_stride,
-                                                             const int* __restrict__ ids,
-                                                             float* __restrict__ logprob, int V) {
-  __shared__ float sm[16], ss[16];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const T* lr = logits + row * row_stride;
-  float m = -INFINITY, s = 0.f;
+__device__ __forceinline__ void lse_thread(const T* __restrict__ lr, int V, float& m, float& s) {
+  const int tid = threadIdx.x;
+  m = -INFINITY;
+  s = 0.f;
   const int nch = V >> 3;
   for (int c = tid; c < nch; c += 1024) {
     float f[8];
@@ -527,6 +528,9 @@ __global__ void __launch_bounds__(1024) token_logprob_kernel(const T* __restrict
     s = s * lse_scale(m, nm) + (l == -INFINITY ? 0.f : __expf(l - nm));
     m = nm;
   }
+}
+__device__ __forceinline__ void lse_waves(float* sm, float* ss, float& m, float& s) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
@@ -537,10 +541,28 @@ __global__ void __launch_bounds__(1024) token_logprob_kernel(const T* __restrict
     ss[wid] = s;
   }
   __syncthreads();
+}
+__device__ __forceinline__ void lse_finish(float& m, float& s, const float* sm, const float* ss) {
+  for (int w = 1; w < 16; ++w) lse_merge(m, s, sm[w], ss[w]);
+}
+template <typename T>
+__device__ __forceinline__ float row_logprob(const T* __restrict__ lr, int id, int V, float m, float s) {
+  return id >= 0 && id < V ? (float)lr[id] - m - logf(s) : NAN;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) token_logprob_kernel(const T* __restrict__ logits, long row_stride,
+                                                             const int* __restrict__ ids,
+                                                             float* __restrict__ logprob, int V) {
+  __shared__ float sm[16], ss[16];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const T* lr = logits + row * row_stride;
+  float m, s;
+  lse_thread<T>(lr, V, m, s);
+  lse_waves(sm, ss, m, s);
   if (tid == 0) {
-    for (int w = 1; w < 16; ++w) lse_merge(m, s, sm[w], ss[w]);
-    const int id = ids[row];
-    logprob[row] = id >= 0 && id < V ? (float)lr[id] - m - logf(s) : NAN;
+    lse_finish(m, s, sm, ss);
+    logprob[row] = row_logprob<T>(lr, ids[row], V, m, s);
   }
 }
 
@@ -555,6 +577,290 @@ PENNY_API int penny_token_logprob(const void* logits, int is_fp32, long row_stri
   } else {
     hipLaunchKernelGGL(token_logprob_kernel<bf16>, dim3(B), dim3(1024), 0, stream, (const bf16*)logits, row_stride,
                        ids, logprob, V);
+  }
+  PENNY_RETURN_LAUNCH();
+}
+
+// Top-N alternatives: per row with n = topn[row] > 0, the chosen token's log-probability (the value
+// token_logprob_kernel reports, by the same code) and the n largest logits of the row in descending
+// order, equal logits by ascending token id (+0 and -0 are equal), each with its log-probability
+// from the same (m, s).  Raw logits at temperature 1: no mask, penalty or filter.  No sort of the
+// vocabulary and no workspace: a radix select over order-preserving integer keys finds the n-th
+// largest key, how many keys lie strictly above it and how many equal it; one more pass collects
+// the keys above and the first members (in index order) of the threshold's plateau -- gathered
+// unordered and ranked by index when the plateau fits LDS, by workgroup scans over sweeps in index
+// order when it does not; at most TOPN_MAX candidates are then ranked in LDS.  Rows with n <= 0 leave
+// after reading their parameter and write nothing.
+//
+// The select only counts keys at or above a floor: the smallest of the 32 half-wave maxima the
+// log-sum-exp pass leaves behind.  32 different elements reach it, so the n-th largest (n <= 20) does
+// too, and of a 128k-entry row a few hundred keys do -- without it every element lands an LDS atomic
+// on the two or three bins of the first digit (sign + exponent), 64 lanes to one address.
+#define TOPN_MAX 20
+static_assert(TOPN_MAX <= 32, "the select's floor counts on 32 half-wave maxima");
+#define TOPN_EQ_CAP 2048   // plateau members gathered unordered (<= the 16 x 256 histogram words)
+
+__device__ __forceinline__ uint32_t tkey(float f) { return fkey(f == 0.f ? 0.f : f); }   // -0 -> +0
+
+// every (index, element) of the row once, 16 B per lane then the tail (V not a multiple of 8)
+template <typename T, typename F>
+__device__ __forceinline__ void row_foreach(const T* __restrict__ lr, int V, F&& fn) {
+  const int nch = V >> 3;
+  for (int c = threadIdx.x; c < nch; c += 1024) {
+    float f[8];
+    load8<T>(lr + c * 8, f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) fn(c * 8 + k, f[k]);
+  }
+  for (int loc = (V & ~7) + threadIdx.x; loc < V; loc += 1024) fn(loc, (float)lr[loc]);
+}
+
+// 256 integer bins (ascending digit) -> the digit whose bin holds the `want`-th key counting from
+// the TOP (1 <= want <= the bins' total), the count above that bin and the count in it.  One wave,
+// as find_from_top.
+__device__ __forceinline__ void find_kth_from_top(const uint32_t* bins, uint32_t want, int& digit, uint32_t& above,
+                                                  uint32_t& inbin) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t b0 = bins[4 * lane], b1 = bins[4 * lane + 1], b2 = bins[4 * lane + 2], b3 = bins[4 * lane + 3];
+  const uint32_t seg = b0 + b1 + b2 + b3;
+  uint32_t suf = seg;                                // inclusive suffix sum over lanes >= l
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_down(suf, o, 64);
+    if (lane + o < 64) suf += v;
+  }
+  const uint32_t abv = suf - seg;
+  unsigned long long hit = __ballot(abv < want && want <= suf);
+  if (hit == 0) hit = __ballot(seg > 0u);            // want beyond the total: the lowest nonzero bin
+  const int src = hit ? (int)__ffsll((long long)hit) - 1 : 0;
+  uint32_t a = __shfl(abv, src, 64);
+  const uint32_t c3 = __shfl(b3, src, 64), c2 = __shfl(b2, src, 64), c1 = __shfl(b1, src, 64);
+  uint32_t c = __shfl(b0, src, 64);
+  int d = 4 * src;
+  if (a + c3 >= want) d += 3, c = c3;
+  else if ((a += c3, a + c2 >= want)) d += 2, c = c2;
+  else if ((a += c2, a + c1 >= want)) d += 1, c = c1;
+  else a += c1;
+  digit = d;
+  above = a;
+  inbin = c;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) topn_logprob_kernel(const T* __restrict__ logits, long row_stride,
+                                                            const int* __restrict__ ids,
+                                                            const int* __restrict__ topn, int max_n,
+                                                            float* __restrict__ logprob, int* __restrict__ top_ids,
+                                                            float* __restrict__ top_lp, int V) {
+  __shared__ uint32_t hist[16][256];     // per-wave digit counts
+  __shared__ uint32_t bins[256];
+  __shared__ float sm[16], ss[16];
+  __shared__ float s_ms[2];              // the row's (m, s)
+  __shared__ float s_hmax[32];           // half-wave maxima
+  __shared__ uint32_t s_prefix, s_want, s_inbin, s_ngt, s_neq;
+  __shared__ uint32_t wsum[2][16];
+  __shared__ uint32_t ckey[TOPN_MAX];
+  __shared__ int cid[TOPN_MAX];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int n = topn[row];
+  if (n <= 0) return;
+  n = min(n, max_n);                     // the entry point checked max_n <= min(TOPN_MAX, V)
+  const T* lr = logits + row * row_stride;
+  float m, s;
+  lse_thread<T>(lr, V, m, s);
+  float hmax = m;                        // never NaN: fmaxf drops one
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) hmax = fmaxf(hmax, __shfl_xor(hmax, o, 64));
+  if ((lane & 31) == 0) s_hmax[tid >> 5] = hmax;
+  lse_waves(sm, ss, m, s);               // its barrier publishes s_hmax too
+  float lo = s_hmax[0];
+#pragma unroll
+  for (int i = 1; i < 32; ++i) lo = fminf(lo, s_hmax[i]);
+  // a half wave without an element (short rows) holds -inf, no element's value: no floor then
+  const uint32_t kfloor = lo == -INFINITY ? 0u : tkey(lo);
+  if (tid == 0) {
+    lse_finish(m, s, sm, ss);
+    logprob[row] = row_logprob<T>(lr, ids[row], V, m, s);
+    s_ms[0] = m;
+    s_ms[1] = s;
+    s_ngt = 0u;
+    s_neq = 0u;
+  }
+  if (tid < TOPN_MAX) {
+    ckey[tid] = 0u;
+    cid[tid] = 0;
+  }
+  // ---- radix select: the n-th largest key and the count strictly above it ----------------------
+  // bf16 logits widen to keys whose low 16 bits follow from the sign: two digits decide
+  constexpr int LAST_SHIFT = sizeof(T) == 2 ? 16 : 0;
+  uint32_t prefix = 0, pmask = 0, want = (uint32_t)n;
+  for (int shift = 24; shift >= LAST_SHIFT; shift -= 8) {
+    for (int i = tid; i < 16 * 256; i += 1024) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    row_foreach<T>(lr, V, [&](int, float v) {
+      const uint32_t key = tkey(v);
+      if (key >= kfloor && (key & pmask) == prefix) atomicAdd(&hist[wid][(key >> shift) & 255], 1u);
+    });
+    __syncthreads();
+    if (tid < 256) {
+      uint32_t t = 0;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) t += hist[w][tid];
+      bins[tid] = t;
+    }
+    __syncthreads();
+    if (wid == 0) {
+      int d;
+      uint32_t above, inbin;
+      find_kth_from_top(bins, want, d, above, inbin);
+      if (lane == 0) {
+        s_prefix = prefix | ((uint32_t)d << shift);
+        s_want = want - above;
+        s_inbin = inbin;
+      }
+    }
+    __syncthreads();
+    prefix = s_prefix;
+    want = s_want;
+    pmask |= 255u << shift;
+  }
+  if (LAST_SHIFT == 16 && !(prefix & 0x80000000u)) prefix |= 0xffffu;   // a negative value's key
+  // ---- collect: every key above the threshold, and the first `need` of its plateau by index -----
+  const uint32_t thr = prefix;
+  const uint32_t need = min(max(want, 1u), (uint32_t)n), ngt = (uint32_t)n - need;
+  // the last digit's bin holds exactly the plateau: every key equal to the threshold
+  const uint32_t neq = s_inbin;
+  if (neq <= TOPN_EQ_CAP) {
+    // a plateau that fits the (now free) histogram memory: one pass without a barrier gathers its
+    // indices in any order, then each is ranked among them and the `need` smallest are taken
+    uint32_t* s_eq = &hist[0][0];
+    row_foreach<T>(lr, V, [&](int idx, float v) {
+      const uint32_t key = tkey(v);
+      if (key > thr) {
+        const uint32_t slot = atomicAdd(&s_ngt, 1u);
+        if (slot < ngt) {
+          ckey[slot] = key;
+          cid[slot] = idx;
+        }
+      } else if (key == thr) {
+        const uint32_t slot = atomicAdd(&s_neq, 1u);
+        if (slot < TOPN_EQ_CAP) s_eq[slot] = (uint32_t)idx;
+      }
+    });
+    __syncthreads();
+    const uint32_t got = min(neq, s_neq);       // == neq: the select counted the same keys
+    for (uint32_t i = tid; i < got; i += 1024) {
+      const uint32_t mine = s_eq[i];
+      uint32_t r = 0;
+      if (neq > need)
+        for (uint32_t j = 0; j < got; ++j) r += s_eq[j] < mine ? 1u : 0u;
+      else
+        r = i;                           // all of it is taken: the final ranking orders it
+      if (r < need) {
+        ckey[ngt + r] = thr;
+        cid[ngt + r] = (int)mine;
+      }
+    }
+  }
+  // a larger plateau: sweeps in index order, a workgroup scan in each giving every member its rank
+  const int nch = V >> 3, nsw = neq <= TOPN_EQ_CAP ? -1 : (nch + 1023) >> 10;
+  uint32_t base = 0;                     // plateau members in the sweeps before this one
+  for (int sw = 0; sw <= nsw; ++sw) {    // sweep nsw is the tail, one element per thread
+    float f[8];
+    int i0 = 0, nv = 0;
+    if (sw < nsw) {
+      const int c = sw * 1024 + tid;
+      if (c < nch) {
+        load8<T>(lr + c * 8, f);
+        i0 = c * 8;
+        nv = 8;
+      }
+    } else {
+      const int loc = (V & ~7) + tid;
+      if (loc < V) {
+        f[0] = (float)lr[loc];
+        i0 = loc;
+        nv = 1;
+      }
+    }
+    uint32_t eq = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (k < nv) {
+        const uint32_t key = tkey(f[k]);
+        if (key > thr) {
+          const uint32_t slot = atomicAdd(&s_ngt, 1u);
+          if (slot < ngt) {
+            ckey[slot] = key;
+            cid[slot] = i0 + k;
+          }
+        } else if (key == thr) {
+          eq |= 1u << k;
+        }
+      }
+    }
+    if (base < need) {                   // uniform: base is the same in every thread
+      const uint32_t cnt = __popc(eq);
+      uint32_t incl = cnt;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      if (lane == 63) wsum[sw & 1][wid] = incl;
+      __syncthreads();
+      uint32_t off = base + incl - cnt, tot = 0;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) {
+        const uint32_t v = wsum[sw & 1][w];
+        if (w < wid) off += v;
+        tot += v;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if ((eq >> k) & 1u) {
+          if (off < need) {
+            ckey[ngt + off] = thr;
+            cid[ngt + off] = i0 + k;
+          }
+          ++off;
+        }
+      }
+      base += tot;
+    }
+  }
+  __syncthreads();
+  // ---- rank the n candidates: (key descending, id ascending) -----------------------------------
+  if (tid < n) {
+    const uint32_t key = ckey[tid];
+    const int id = cid[tid];
+    int rank = 0;
+    for (int i = 0; i < n; ++i) {
+      const uint32_t ki = ckey[i];
+      rank += (i != tid && (ki > key || (ki == key && cid[i] < id))) ? 1 : 0;
+    }
+    top_ids[(size_t)row * TOPN_MAX + rank] = id;
+    top_lp[(size_t)row * TOPN_MAX + rank] = row_logprob<T>(lr, id, V, s_ms[0], s_ms[1]);
+  }
+}
+
+// logits [B, V] bf16 / f32 with 16-B aligned rows (as penny_sample), ids [B], topn [B] int32 (<= 0:
+// the row is skipped) -> logprob [B] f32, top_ids / top_lp [B, TOPN_MAX]; columns >= topn[row] are
+// not written.  max_n: the host's bound on topn (the kernel caps every row at it); max_n > TOPN_MAX
+// or max_n > V is refused.
+PENNY_API int penny_topn_logprob(const void* logits, int is_fp32, long row_stride, const int* ids, const int* topn,
+                                 int max_n, float* logprob, int* top_ids, float* top_lp, int B, int V,
+                                 hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!logits || !ids || !topn || !logprob || !top_ids || !top_lp || V <= 0 || max_n < 0 || max_n > TOPN_MAX ||
+      max_n > V)
+    return (int)hipErrorInvalidValue;
+  if (is_fp32) {
+    hipLaunchKernelGGL(topn_logprob_kernel<float>, dim3(B), dim3(1024), 0, stream, (const float*)logits, row_stride,
+                       ids, topn, max_n, logprob, top_ids, top_lp, V);
+  } else {
+    hipLaunchKernelGGL(topn_logprob_kernel<bf16>, dim3(B), dim3(1024), 0, stream, (const bf16*)logits, row_stride,
+                       ids, topn, max_n, logprob, top_ids, top_lp, V);
   }
   PENNY_RETURN_LAUNCH();
 }

@@ -184,17 +184,23 @@ class EngineLLM(LLMBackend):
             forced = self.tok.encode(text, allow_special=False)[: max_tokens - 1] + ([self.eot] if self.eot is not None else [])
             if grammar is not None:
                 jump = jump_mask(forced, self.tok.decode, grammar, self.eot)
+        top_n = int(kw.get("top_logprobs") or 0)
+        if top_n and not self._can_logprob():          # dropped where logprobs is, under the same warning
+            top_n = 0
         params = SamplingParams(temperature=temperature, max_tokens=max_tokens, forced_output=forced,
                                 forced_jump=jump, grammar=grammar, constraint=self._constraint(tools),
                                 ephemeral_kv=bool(kw.get("ephemeral_kv")),
                                 prompt_lookup=self.prompt_lookup, priority_ts=TURN_START.get(),
-                                logprobs=bool(kw.get("logprobs")) and self._can_logprob(), **self._penalties(kw))
+                                logprobs=(bool(kw.get("logprobs")) and self._can_logprob()) or top_n > 0,
+                                top_logprobs=top_n, **self._penalties(kw))
         out = await self.engine.generate_all(ids, params)
         self._account(kw.get("purpose", "decide"), len(ids), out.seq)
         text = self.tok.decode(out.seq.output_ids)
         lps = list(out.seq.output_logprobs) if params.logprobs else None
+        tops = list(getattr(out.seq, "output_top_logprobs", None) or []) if top_n else None
         return LLMResult(text=text, tool_calls=parse_tool_calls(text, tools), prompt_tokens=len(ids),
-                         completion_tokens=len(out.seq.output_ids), logprobs=lps, mean_logprob=mean_logprob(lps))
+                         completion_tokens=len(out.seq.output_ids), logprobs=lps, mean_logprob=mean_logprob(lps),
+                         top_logprobs=tops, token_ids=list(out.seq.output_ids))
 
     async def astream(self, messages, temperature=0.5, max_tokens=512, **kw) -> AsyncIterator[str]:
         n = self.respond_tokens or max_tokens

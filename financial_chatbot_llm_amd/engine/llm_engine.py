@@ -8,6 +8,7 @@ other ranks).  Decode-size TP all-reduces take the custom one-shot xGMI kernel b
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import time
 from collections import deque
@@ -21,6 +22,7 @@ from ..config import EngineConfig
 from ..models import build_model
 from ..models.common import KVCache
 from ..ops.attention import KV_BS
+from ..ops.sampling import TOPN_MAX
 from ..parallel import comm
 from ..parallel.dist import state as pstate
 from ..utils.logging import get_logger
@@ -48,6 +50,10 @@ class StepOutput:
     # parallel to new_token_ids when the request asked (SamplingParams.logprobs): the token's
     # log-probability, None for a token appended without a sample; None when it did not ask
     new_logprobs: Optional[List[Optional[float]]] = None
+    # parallel to new_token_ids when the request asked for alternatives (SamplingParams.top_logprobs):
+    # the token's N (token id, log-probability) pairs, None for a token appended without a sample;
+    # None when it did not ask
+    new_top_logprobs: Optional[List[Optional[List[Tuple[int, float]]]]] = None
 
 
 @dataclass
@@ -184,6 +190,12 @@ class LLMEngine:
     def add_request(self, request_id: str, prompt_ids: Seq[int], params: SamplingParams) -> Sequence:
         if not prompt_ids:
             raise ValueError("empty prompt")
+        # argument checks first: a refused request leaves nothing behind (no automaton registered)
+        tn = params.top_logprobs
+        if isinstance(tn, bool) or not isinstance(tn, int) or not 0 <= tn <= TOPN_MAX:
+            raise ValueError(f"top_logprobs must be an integer in 0..{TOPN_MAX}, got {tn!r}")
+        if tn > self.model.cfg.vocab_size:
+            raise ValueError(f"top_logprobs = {tn} exceeds the vocabulary of {self.model.cfg.vocab_size} tokens")
         max_prompt = self.cfg.max_model_len - 1
         seq = Sequence(request_id, list(prompt_ids)[-max_prompt:], params)
         if params.constraint is not None:
@@ -194,6 +206,13 @@ class LLMEngine:
                     seq.fsm_off = self.runner.register_automaton(params.constraint)
                 except ValueError as e:            # tables full / other tokenizer: decode as before
                     logger.warning(f"request {request_id}: constraint dropped ({e}); decoding unconstrained")
+        if tn > 0:
+            if self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None:
+                raise NotImplementedError("top_logprobs: TP / CP engines sample vocabulary-parallel [B, 2] pairs, "
+                                          "which carry no alternatives yet")
+            if not params.logprobs:                # alternatives imply the token's own value
+                params = dataclasses.replace(params, logprobs=True)
+                seq.params = params
         if params.logprobs and (self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None):
             raise NotImplementedError("generation log-probabilities: TP / CP engines sample vocabulary-parallel "
                                       "[B, 2] pairs, which do not carry them yet")
@@ -560,26 +579,41 @@ class LLMEngine:
         return None
 
     @staticmethod
-    def _emit(seq: Sequence, new: List[int], lps: List[Optional[float]], reason: Optional[str]) -> StepOutput:
-        """The StepOutput of ``new``; a request that asked for log-probabilities records ``lps``
-        (parallel to ``new``) beside its output."""
+    def _emit(seq: Sequence, new: List[int], rows: List[Optional[tuple]], reason: Optional[str]) -> StepOutput:
+        """The StepOutput of ``new``; a request that asked for log-probabilities records the values of
+        ``rows`` (parallel to ``new``: the sampled row's (log-probability, alternatives), None for a
+        token appended without a sample) beside its output."""
         if not seq.params.logprobs:
             return StepOutput(seq.request_id, new, reason is not None, reason, seq)
-        assert len(lps) == len(new)
+        assert len(rows) == len(new)
+        lps = [None if r is None else r[0] for r in rows]
         seq.output_logprobs.extend(lps)
-        return StepOutput(seq.request_id, new, reason is not None, reason, seq, list(lps))
+        tops = None
+        if seq.params.top_logprobs > 0:
+            tops = [None if r is None else r[1] for r in rows]
+            seq.output_top_logprobs.extend(tops)
+        return StepOutput(seq.request_id, new, reason is not None, reason, seq, lps, tops)
+
+    @staticmethod
+    def _row_values(pending) -> Optional[List[tuple]]:
+        """Per sampled row of a collected step: (log-probability, top-N alternatives or None); None
+        when the step carries no log-probabilities."""
+        if pending.logprobs is None:
+            return None
+        tops = pending.top_logprobs if pending.top_logprobs is not None else [None] * len(pending.logprobs)
+        return list(zip(pending.logprobs, tops))
 
     def _resolve(self, samplers: List[Sequence], sampled: List[int],
-                 logprobs: Optional[List[float]] = None) -> List[StepOutput]:
+                 logprobs: Optional[List[tuple]] = None) -> List[StepOutput]:
         now = time.perf_counter()
         outs: List[StepOutput] = []
         for seq, row, toks in self._group(samplers, sampled):
             tok = toks[-1]
             if seq.finished:                   # aborted (or finished) while in flight
                 continue
-            # this sequence's rows of the step's log-probabilities (a step none of whose requests
-            # asked carries none)
-            rlp: List[Optional[float]] = (logprobs[row:row + len(toks)] if logprobs is not None
+            # this sequence's rows of the step's values, (log-probability, alternatives) per row as
+            # _row_values pairs them (a step none of whose requests asked carries none)
+            rlp: List[Optional[tuple]] = (logprobs[row:row + len(toks)] if logprobs is not None
                                           else [None] * len(toks))
             was_sampled = False
             sat_out = False                    # not in the step launched just now: may draft
@@ -634,8 +668,9 @@ class LLMEngine:
         return outs
 
     @staticmethod
-    def _verified_logprobs(seq: Sequence, rlp: List[Optional[float]], j: int) -> List[Optional[float]]:
-        """Log-probabilities of a verified chunk's j accepted draft tokens and its bonus token: an
+    def _verified_logprobs(seq: Sequence, rlp: List[Optional[tuple]], j: int) -> List[Optional[tuple]]:
+        """The row values -- (log-probability, top-N alternatives or None) per sampled row, as
+        ``_row_values`` pairs them -- of a verified chunk's j accepted draft tokens and its bonus token: an
         accepted draft token IS the sample of its row, so rows 0 .. j are the tokens kept.  A
         teacher-forced chunk is verified against the script, not against samples: its accepted
         tokens carry None."""
@@ -677,7 +712,7 @@ class LLMEngine:
             with marker("engine.wait"):
                 res = prev[2].result()
             with marker("engine.resolve"):
-                outs = self._resolve(prev[1], res, prev[2].logprobs)
+                outs = self._resolve(prev[1], res, self._row_values(prev[2]))
         self._inflight = launched
         t3 = time.perf_counter()
         tm = self.timing
@@ -698,7 +733,7 @@ class LLMEngine:
         t1 = time.perf_counter()
         pending = self.runner.launch(si)
         sampled = pending.result()
-        logprobs = pending.logprobs
+        logprobs = self._row_values(pending)
         now = time.perf_counter()
         tm = self.timing
         tm["prepare_s"] += t1 - t0
@@ -712,9 +747,9 @@ class LLMEngine:
         for seq, row, toks in self._group(samplers, sampled):
             acc: List[int] = []
             tok = toks[-1]
-            rlp: List[Optional[float]] = (logprobs[row:row + len(toks)] if logprobs is not None
+            rlp: List[Optional[tuple]] = (logprobs[row:row + len(toks)] if logprobs is not None
                                           else [None] * len(toks))
-            lps: List[Optional[float]] = [rlp[-1]]
+            lps: List[Optional[tuple]] = [rlp[-1]]
             if seq.spec_rows > 1:
                 acc, tok = self._verify(seq, toks)
                 lps = self._verified_logprobs(seq, rlp, len(acc))
@@ -860,6 +895,7 @@ class LLMEngine:
                 "constrained_tokens": self.runner.stats["constrained_tokens"],
                 "constrained_steps": self.runner.stats["constrained_steps"],
                 "logprob_steps": self.runner.stats["logprob_steps"],
+                "top_logprob_steps": self.runner.stats["top_logprob_steps"],
                 "penalty_steps": self.runner.stats["penalty_steps"],
                 "penalty_rows": self.runner.stats["penalty_rows"],
                 "penalty_waiting": len(self._pen_queue),

@@ -24,6 +24,7 @@ from .. import ops
 from ..models.common import AttentionMetadata, KVCache
 from ..ops import attention as _attn
 from ..ops.attention import KV_BS, DecodeWorkspace, mark_shared_blocks, prefill_plan
+from ..ops.sampling import TOPN_MAX
 from ..parallel import comm
 from ..utils.logging import get_logger
 from ..utils.profiling import marker
@@ -73,6 +74,10 @@ class StepInputs:
     pen: Optional[np.ndarray] = None
     pen_params: Optional[np.ndarray] = None
     pen_add: Optional[np.ndarray] = None
+    # [S] int32 top-N alternatives asked for per sampled row (SamplingParams.top_logprobs; None: no row
+    # asks).  Such a step samples as it would without them, then reads the alternatives -- and those
+    # rows' log-probabilities -- off the step's raw logits (``ModelRunner._sample``).  Not on the C4 wire.
+    topn: Optional[np.ndarray] = None
 
     @property
     def num_prefill_tokens(self) -> int:
@@ -81,7 +86,7 @@ class StepInputs:
     # -- C4 wire format: one flat byte buffer (no pickling) ------------------------------------
     _ARRAYS = ("ids", "positions", "slots", "cu_q", "ctx_p", "bt_p", "ctx_d", "bt_d", "logits_idx", "temps",
                "seeds", "top_k", "top_p", "src", "pwork", "fsm_state")
-    _LOCAL = ("pen", "pen_params", "pen_add")     # staged with the step's arrays, never sent
+    _LOCAL = ("pen", "pen_params", "pen_add", "topn")     # staged with the step's arrays, never sent
 
     def pack(self) -> np.ndarray:
         """[header int64: max_q_len, then (dtype code, rows, cols) per array] + raw array bytes."""
@@ -222,8 +227,8 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     slot_parts: List[np.ndarray] = []
     cu = [0]
     ctx_p, tables_p = [], []
-    logits_idx, temps, seeds, tk, tp, fsm = [], [], [], [], [], []
-    want_lp = False
+    logits_idx, temps, seeds, tk, tp, fsm, tn = [], [], [], [], [], [], []
+    want_lp = want_tn = False
     pen = _PenRows()
     max_q = 0
     for seq, start, n in batch.prefill:
@@ -245,6 +250,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
             r = sample_rows(seq, n)
             k0 = len(seq.output_ids) - r + 1
             want_lp = want_lp or seq.params.logprobs
+            want_tn = want_tn or seq.params.top_logprobs > 0
             for i in range(r):
                 logits_idx.append(cu[-1] - r + i)
                 temps.append(seq.params.temperature)
@@ -252,6 +258,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
                 tk.append(seq.params.top_k)
                 tp.append(seq.params.top_p)
                 fsm.append(fsm_code(seq, k0 + i))
+                tn.append(seq.params.top_logprobs)
                 pen.row(seq, k0 + i)
     Tp = cu[-1]
     ids_d, pos_d, slots_d = [], [], []
@@ -274,8 +281,10 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
         tk.append(seq.params.top_k)
         tp.append(seq.params.top_p)
         fsm.append(fsm_code(seq, len(seq.output_ids)))
+        tn.append(seq.params.top_logprobs)
         pen.row(seq, len(seq.output_ids))
         want_lp = want_lp or seq.params.logprobs
+        want_tn = want_tn or seq.params.top_logprobs > 0
 
     i32 = lambda x: np.asarray(x, np.int32)  # noqa: E731
     cat = lambda parts, tail: np.concatenate(parts + [i32(tail)]) if parts else i32(tail)  # noqa: E731
@@ -287,7 +296,8 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     return StepInputs(cat(ids_parts, ids_d), cat(pos_parts, pos_d), cat(slot_parts, slots_d), i32(cu), i32(ctx_p),
                       _table(tables_p), max_q, i32(ctx_d), bt_d, np.asarray(logits_idx, np.int64),
                       np.asarray(temps, np.float32), np.asarray(seeds, np.int64), i32(tk), np.asarray(tp, np.float32),
-                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None, bool(want_lp), *pen.arrays())
+                      src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None, bool(want_lp), *pen.arrays(),
+                      i32(tn) if want_tn else None)
 
 
 def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
@@ -310,22 +320,35 @@ class CollectiveTimeout(RuntimeError):
 class PendingStep:
     """Sampled ids of a launched step (host copy in flight).  A step that sampled with
     log-probabilities carries them in the same host buffer, ``lp_off`` int32 slots in (f32 bits), or
-    in ``cpu_lp`` on the CPU: ``result()`` leaves them in ``logprobs`` ([n] floats, else None)."""
+    in ``cpu_lp`` on the CPU: ``result()`` leaves them in ``logprobs`` ([n] floats, else None).  A step
+    with top-N rows (``topn``: its [n] per-row counts) carries their [n, TOPN_MAX] ids and values behind
+    them, ``tn_off`` slots in (``cpu_topn`` on the CPU): ``top_logprobs`` is then one list of
+    (token id, log-probability) pairs per row, None for a row that asked for none."""
 
     def __init__(self, cpu_out: Optional[torch.Tensor], n: int, host: Optional[torch.Tensor], event,
                  start_event=None, stats: Optional[Dict] = None, key: str = "", check_err: bool = False,
-                 lp_off: int = -1, cpu_lp: Optional[torch.Tensor] = None):
+                 lp_off: int = -1, cpu_lp: Optional[torch.Tensor] = None, topn: Optional[np.ndarray] = None,
+                 tn_off: int = -1, cpu_topn=None):
         self._cpu, self.n, self._host, self._event = cpu_out, n, host, event
         self._start, self._stats, self._key = start_event, stats, key
         self._check_err = check_err
         self._lp_off, self._cpu_lp = lp_off, cpu_lp
+        self._topn, self._tn_off, self._cpu_topn = topn, tn_off, cpu_topn
         self.logprobs: Optional[List[float]] = None
+        self.top_logprobs: Optional[List[Optional[List[Tuple[int, float]]]]] = None
+
+    def _pairs(self, ids: torch.Tensor, lps: torch.Tensor) -> None:
+        il, vl = ids.tolist(), lps.tolist()
+        self.top_logprobs = [list(zip(il[r][:k], vl[r][:k])) if k > 0 else None
+                             for r, k in enumerate(self._topn.tolist())]
 
     def result(self) -> List[int]:
         if self.n == 0:
             return []
         if self._cpu_lp is not None:
             self.logprobs = self._cpu_lp.tolist()
+        if self._cpu_topn is not None:
+            self._pairs(*self._cpu_topn)
         if self._cpu is not None:
             return self._cpu.tolist()
         if self._event is not None:
@@ -346,25 +369,34 @@ class PendingStep:
                                     "hidden states are stale")
         if self._lp_off >= 0:
             self.logprobs = self._host[self._lp_off:self._lp_off + self.n].view(torch.float32).tolist()
+        if self._tn_off >= 0:
+            w = self.n * TOPN_MAX
+            self._pairs(self._host[self._tn_off:self._tn_off + w].view(self.n, TOPN_MAX),
+                        self._host[self._tn_off + w:self._tn_off + 2 * w].view(torch.float32).view(self.n, TOPN_MAX))
         return self._host[:self.n].tolist()
 
 
 class Sampled(NamedTuple):
     """What the sampling stage leaves on the device: the token per row, the next automaton states
-    (sampler "fsm" only) and the tokens' log-probabilities (only when asked for)."""
+    (sampler "fsm" only), the tokens' log-probabilities (only when asked for) and the top-N rows'
+    alternatives ([rows, TOPN_MAX] ids and values; only in a step that holds such a row)."""
     out: torch.Tensor
     state_out: Optional[torch.Tensor] = None
     logprob: Optional[torch.Tensor] = None
+    top_ids: Optional[torch.Tensor] = None
+    top_lp: Optional[torch.Tensor] = None
 
 
 class _DecodeGraph:
     def __init__(self, graph, B: int, out: torch.Tensor, fused: bool = False,
-                 state_out: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None):
+                 state_out: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None,
+                 top_ids: Optional[torch.Tensor] = None, top_lp: Optional[torch.Tensor] = None):
         # fused: the graph samples inside the LM head (no top-k / top-p support)
         # state_out: the constrained twin's next automaton states (beside ``out``)
         # logprob: a log-probability twin's [B] f32 values (beside ``out``)
+        # top_ids, top_lp: a top-N twin's [B, TOPN_MAX] alternatives
         self.graph, self.B, self.out, self.fused, self.state_out = graph, B, out, fused, state_out
-        self.logprob = logprob
+        self.logprob, self.top_ids, self.top_lp = logprob, top_ids, top_lp
 
 
 # Which sampler a step runs, and which captured graph holds it, decided from booleans alone.  Samplers:
@@ -391,19 +423,25 @@ def default_graph_kind(shard: bool, fused: bool) -> str:
 
 
 DEFAULT_GRAPH, EAGER = "default", "eager"
+TOPN_TWIN = "+topn"      # suffix of a twin's sampler name: the same sampling stage, then the alternatives
 
 
-def graph_plan(fsm: bool, filters: bool, lp: bool, bucket_fused: bool, tp: bool, pen: bool = False):
+def graph_plan(fsm: bool, filters: bool, lp: bool, bucket_fused: bool, tp: bool, pen: bool = False,
+               topn: bool = False):
     """What runs a pure-decode step whose bucket's default graph is ``bucket_fused`` or not:
     DEFAULT_GRAPH, EAGER, or the (sampler, lp) of the bucket's twin graph, captured on the first step
     that needs it.  The default graph has no automaton, no penalties, no log-probabilities and, when
     fused, no top-k / top-p; twins exist at TP = 1 only, and none holds penalties and the automaton
-    together (such a step runs eagerly)."""
+    together (such a step runs eagerly).  ``topn`` (a row asks for alternatives, which implies ``lp``)
+    picks the twin the step would replay without it, with ``TOPN_TWIN`` appended to the sampler's name:
+    a graph of its own, so the plain twins stay as they are."""
+    lp = lp or topn
     if not (fsm or pen or lp or (filters and bucket_fused)):
         return DEFAULT_GRAPH
     if tp or (fsm and pen):
         return EAGER
-    return ("fsm" if fsm else "pen" if pen else "logits" if filters or not bucket_fused else "fused"), lp
+    kind = "fsm" if fsm else "pen" if pen else "logits" if filters or not bucket_fused else "fused"
+    return kind + (TOPN_TWIN if topn else ""), lp
 
 
 class ModelRunner:
@@ -446,13 +484,14 @@ class ModelRunner:
         # request (``ensure_penalty_table``), and the static inputs of the "pen" graph twins
         self.pen_table: Optional[ops.PenaltyTable] = None
         self._pen_static = None
+        self._topn_static = None                          # per-row N of the top-N graph twins
         self._static = None
         self.graph_pool = None
         self.stats = {"steps": 0, "graph_steps": 0, "tokens": 0, "prefill_steps": 0, "prefill_step_tokens": 0,
                       "prefill_tile_pad_rows": 0, "prefill_m_hist": [0] * len(PREFILL_M_BUCKETS), "gpu_graph_s": 0.0, "gpu_eager_s": 0.0,
                       "gpu_idle_s": 0.0, "gpu_idle_gaps": 0, "_prev_end_ev": None, "overlap_steps": 0,
                       "constrained_steps": 0, "constrained_tokens": 0, "logprob_steps": 0,
-                      "penalty_steps": 0, "penalty_rows": 0}
+                      "penalty_steps": 0, "penalty_rows": 0, "top_logprob_steps": 0}
         # TP prefill steps of >= overlap_min_rows rows run as two micro-batches whose all-reduces
         # overlap the other half's compute (PENNY_TP_OVERLAP=0 disables)
         self.tp_overlap = os.environ.get("PENNY_TP_OVERLAP", "1") == "1"
@@ -468,6 +507,7 @@ class ModelRunner:
         # one slot past the sampled ids carries the custom all-reduce's timeout flag back with them, and
         # the slots from _lp_off on the step's log-probabilities (f32 bits): one buffer, one event
         self._lp_off = self.max_samplers + 1
+        self._tn_off = 2 * self.max_samplers + 1      # top-N alternatives: allocated with the first such step
         self._pinned_out = ([torch.zeros(2 * self.max_samplers + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
                             if self.on_gpu else None)
         self._out_flip = 0
@@ -702,22 +742,28 @@ class ModelRunner:
             self.stats["fused_lm_head_steps"] = self.stats.get("fused_lm_head_steps", 0) + 1
         return self._sample(hs, kind, self._to_dev(si.temps), self._to_dev(si.seeds),
                             self._to_dev(si.top_k) if filt else None, self._to_dev(si.top_p) if filt else None,
-                            state, si.want_logprobs, pen)
+                            state, si.want_logprobs, pen, self._to_dev(si.topn) if si.topn is not None else None)
 
     def _sample(self, hs: torch.Tensor, kind: str, temps: torch.Tensor, seeds: torch.Tensor,
                 top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
-                state: Optional[torch.Tensor] = None, lp: bool = False, pen=None) -> Sampled:
+                state: Optional[torch.Tensor] = None, lp: bool = False, pen=None,
+                topn: Optional[torch.Tensor] = None) -> Sampled:
         """The one sampling stage, of eager steps and captured graphs alike: one token per hidden row
         ``hs`` through the sampler ``kind`` (see ``sampler_kind``).  ``lp``: the log-probability form
         -- the same tokens, the fused LM head still without logits, a step that holds its logits
-        reading the values off them right after the (untouched) sampler."""
+        reading the values off them right after the (untouched) sampler.  ``topn`` ([rows] int32, > 0
+        where a row asks for alternatives; implies ``lp``): the stage runs as without it, then
+        ``ops.topn_logprobs`` reads the raw logits -- the ones the stage holds, else (the fused LM head)
+        the LM-head logits GEMM's, computed after the sampler -- and replaces those rows'
+        log-probabilities by the value from that same row of logits; the other rows keep theirs."""
         m = self.model
+        lp = lp or topn is not None
         if kind == "shard":
             return Sampled(m.sample_vocab_parallel(hs, temps, seeds))
         if kind == "fused":
             if lp:
                 out, logprob = ops.lm_head_sample_logprob(hs, m.lm_weight(), temps, seeds, wt=self._lm_tiled())
-                return Sampled(out, None, logprob)
+                return self._with_topn(Sampled(out, None, logprob), hs, None, topn)
             return Sampled(ops.lm_head_sample(hs, m.lm_weight(), temps, seeds, wt=self._lm_tiled()))
         logits = m.logits(hs).contiguous()
         state_out = None
@@ -736,7 +782,23 @@ class ModelRunner:
             out, state_out = ops.sample_constrained(chosen, temps, seeds, state, self.fsm, top_k=top_k, top_p=top_p)
         else:                       # device-side top-k / top-p threshold when given
             out = ops.sample(chosen, temps, seeds, top_k=top_k, top_p=top_p)
-        return Sampled(out, state_out, ops.token_logprobs(logits, out) if lp else None)
+        return self._with_topn(Sampled(out, state_out, ops.token_logprobs(logits, out) if lp else None), hs, logits,
+                               topn)
+
+    def _with_topn(self, sampled: Sampled, hs: torch.Tensor, logits: Optional[torch.Tensor],
+                   topn: Optional[torch.Tensor]) -> Sampled:
+        """The alternatives of a step's top-N rows, after its sampling stage: off ``logits`` (raw, as
+        the stage holds them) or, None, the LM-head logits of ``hs``."""
+        if topn is None:
+            return sampled
+        if logits is None:
+            logits = self.model.logits(hs).contiguous()
+        n = hs.shape[0]
+        top_ids = torch.empty((n, TOPN_MAX), dtype=torch.int32, device=hs.device)
+        top_lp = torch.empty((n, TOPN_MAX), dtype=torch.float32, device=hs.device)
+        logprob = sampled.logprob.float().contiguous()      # the kernel writes the top-N rows' entries only
+        ops.topn_logprobs(logits, sampled.out, topn, out=(logprob, top_ids, top_lp))
+        return sampled._replace(logprob=logprob, top_ids=top_ids, top_lp=top_lp)
 
     def execute(self, si: StepInputs) -> List[int]:
         """Run one step; returns the sampled token per entry of ``si.logits_idx``."""
@@ -783,20 +845,22 @@ class ModelRunner:
         graph = G is not None
         if graph:
             with marker(f"decode.graph[{si.num_decode}]"):
-                out, so, lpv = self._graph_decode(si, G)
+                out, so, lpv, tid, tlp = self._graph_decode(si, G)
         else:
             with marker(f"forward.eager[{len(si.ids)}]"):
                 if si.num_prefill_tokens and si.pwork is None and self.on_gpu:
                     si.pwork = prefill_plan(si.cu_q, si.ctx_p, self.G, self.model.hkv)
                 self._stage_inputs(si)
                 try:
-                    out, so, lpv = self.logits_and_sample(si)
+                    out, so, lpv, tid, tlp = self.logits_and_sample(si)
                 finally:
                     self._staged = None
         n = len(si.logits_idx)
         self.last_sampled[:n].copy_(out[:n].to(torch.int32), non_blocking=True)
         if si.want_logprobs:
             self.stats["logprob_steps"] += 1
+        if si.topn is not None:
+            self.stats["top_logprob_steps"] += 1
         if si.pen is not None:
             self._count_penalty_step(si)
         if si.fsm_state is not None:
@@ -807,15 +871,26 @@ class ModelRunner:
         if not self.on_gpu:
             cpu = out[:n].clone()
             cpu_lp = lpv[:n].float().clone() if lpv is not None else None
+            tn = dict(topn=si.topn, cpu_topn=(tid[:n], tlp[:n])) if si.topn is not None else {}
             if ar is not None:           # a host-side stand-in (tests): its flag is host memory
                 return PendingStep(None, n, torch.cat([cpu.to(torch.int32), ar.err.to(torch.int32)[:1]]), None,
-                                   check_err=True, cpu_lp=cpu_lp)
-            return PendingStep(cpu, n, None, None, cpu_lp=cpu_lp)
+                                   check_err=True, cpu_lp=cpu_lp, **tn)
+            return PendingStep(cpu, n, None, None, cpu_lp=cpu_lp, **tn)
+        if si.topn is not None and self._pinned_out[0].numel() < self._tn_off + 2 * TOPN_MAX * self.max_samplers:
+            # the first step with top-N rows: the host buffers grow by the alternatives' region (a step
+            # in flight keeps the buffer it was given)
+            self._pinned_out = [torch.zeros(self._tn_off + 2 * TOPN_MAX * self.max_samplers,
+                                            dtype=torch.int32).pin_memory() for _ in range(2)]
         host = self._pinned_out[self._out_flip]
         self._out_flip ^= 1
         host[:n].copy_(out[:n], non_blocking=True)
         if lpv is not None:
             host[self._lp_off:self._lp_off + n].view(torch.float32).copy_(lpv[:n], non_blocking=True)
+        if si.topn is not None:        # [n, TOPN_MAX] ids then values, sized by this step's rows
+            w = n * TOPN_MAX
+            host[self._tn_off:self._tn_off + w].view(n, TOPN_MAX).copy_(tid[:n], non_blocking=True)
+            host[self._tn_off + w:self._tn_off + 2 * w].view(torch.float32).view(n, TOPN_MAX).copy_(
+                tlp[:n], non_blocking=True)
         if ar is not None:
             # the xGMI all-reduce never raises from the device: a peer that missed its bounded wait
             # sets ar.err and the step's sums are stale, so the flag rides the per-step host sync
@@ -823,7 +898,8 @@ class ModelRunner:
         ev = end_ev
         ev.record()
         return PendingStep(None, n, host, ev, start_ev, self.stats, "gpu_graph_s" if graph else "gpu_eager_s",
-                           check_err=ar is not None, lp_off=self._lp_off if lpv is not None else -1)
+                           check_err=ar is not None, lp_off=self._lp_off if lpv is not None else -1,
+                           topn=si.topn, tn_off=self._tn_off if si.topn is not None else -1)
 
     def _forward_only(self, si: StepInputs) -> None:
         self._hidden(si)
@@ -924,6 +1000,9 @@ class ModelRunner:
         """One decode step of bucket B on the static inputs, sampled by ``kind`` (None: the bucket's
         default sampler, decided here and returned)."""
         s = self._static
+        topn = None
+        if kind is not None and kind.endswith(TOPN_TWIN):
+            kind, topn = kind[:-len(TOPN_TWIN)], self._topn_static["n"][:B]
         fsm = kind == "fsm"
         pen = None
         if kind == "pen":     # pending rows -> tokens, before the sampler of this graph writes last_sampled
@@ -950,7 +1029,7 @@ class ModelRunner:
         # rows (k=0, p=1) exit after reading their parameters; under TP such rows replay eagerly
         filt = kind in ("fsm", "logits", "pen")
         return kind, self._sample(h, kind, s["temps"][:B], s["seeds"][:B], s["top_k"][:B] if filt else None,
-                                  s["top_p"][:B] if filt else None, s["fsm"][:B] if fsm else None, lp, pen)
+                                  s["top_p"][:B] if filt else None, s["fsm"][:B] if fsm else None, lp, pen, topn)
 
     def _capture(self, B: int, kind: Optional[str] = None, lp: bool = False) -> _DecodeGraph:
         for _ in range(2):      # warm up (allocator + hipBLASLt heuristics) outside the capture
@@ -961,7 +1040,8 @@ class ModelRunner:
             kind, sampled = self._run_static(B, kind, lp)
         if self.graph_pool is None:
             self.graph_pool = g.pool()
-        return _DecodeGraph(g, B, sampled.out, kind in ("shard", "fused"), sampled.state_out, sampled.logprob)
+        return _DecodeGraph(g, B, sampled.out, kind in ("shard", "fused"), sampled.state_out, sampled.logprob,
+                            sampled.top_ids, sampled.top_lp)
 
     def capture_graphs(self) -> None:
         if not self.use_graphs:
@@ -983,7 +1063,7 @@ class ModelRunner:
         B = self._bucket(si.num_decode)
         G = self.graphs[B]
         plan = graph_plan(si.fsm_state is not None, self._has_filters(si), si.want_logprobs, G.fused,
-                          getattr(self.model, "tp_size", 1) > 1, si.pen is not None)
+                          getattr(self.model, "tp_size", 1) > 1, si.pen is not None, si.topn is not None)
         if plan == DEFAULT_GRAPH:
             return G
         if plan == EAGER:
@@ -1008,6 +1088,9 @@ class ModelRunner:
         are restored after."""
         B, kind, lp = key
         s = self._static
+        if kind.endswith(TOPN_TWIN):
+            self._alloc_topn_static()      # no row asks (N = 0) until the replay fills them in
+            kind = kind[:-len(TOPN_TWIN)]
         if kind == "pen":
             self._alloc_pen_static()       # no row penalised (slot -1) until the replay fills them in
         saved = (s["slots"][:B].clone(), s["src"][:B].clone(), s["fsm"][:B].clone())
@@ -1015,7 +1098,7 @@ class ModelRunner:
         s["src"][:B].fill_(-1)
         s["fsm"][:B].fill_(-1)
         try:
-            self.twins[key] = self._capture(B, kind, lp)
+            self.twins[key] = self._capture(B, key[1], lp)
         finally:                                  # the step in flight keeps its inputs either way
             s["slots"][:B].copy_(saved[0])
             s["src"][:B].copy_(saved[1])
@@ -1038,6 +1121,25 @@ class ModelRunner:
                 "flip": 0,
             }
         self._pen_static["i32"].fill_(-1)
+
+    def _alloc_topn_static(self) -> None:
+        """Static per-row N of the top-N twins ([B] int32, one pinned copy per such graph step),
+        allocated with the first of them."""
+        B = self.max_decode_batch
+        if self._topn_static is None:
+            self._topn_static = {"n": torch.zeros(B, dtype=torch.int32, device=self.device),
+                                 "pinned": [torch.zeros(B, dtype=torch.int32).pin_memory() for _ in range(2)],
+                                 "flip": 0}
+        self._topn_static["n"].zero_()
+
+    def _stage_topn_static(self, si: StepInputs, B: int) -> None:
+        ts = self._topn_static
+        pin = ts["pinned"][ts["flip"]]
+        ts["flip"] ^= 1
+        a = pin.numpy()
+        a[:B] = 0
+        a[:si.num_decode] = si.topn
+        ts["n"].copy_(pin, non_blocking=True)
 
     def _stage_pen_static(self, si: StepInputs, B: int) -> None:
         """The penalty inputs of a "pen" twin's replay; ``pen_add`` is counted eagerly in front of it."""
@@ -1099,6 +1201,8 @@ class ModelRunner:
         s["seeds"].copy_(self._pinned_l, non_blocking=True)
         if si.pen is not None:             # only a "pen" twin is chosen for such a step (graph_plan)
             self._stage_pen_static(si, B)
+        if si.topn is not None:            # likewise a top-N twin
+            self._stage_topn_static(si, B)
         G.graph.replay()
         self.stats["graph_steps"] += 1
-        return Sampled(G.out[:n], G.state_out, G.logprob)
+        return Sampled(G.out[:n], G.state_out, G.logprob, G.top_ids, G.top_lp)

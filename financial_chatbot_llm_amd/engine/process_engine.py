@@ -49,6 +49,7 @@ class RemoteSeq:
     output_ids: List[int] = field(default_factory=list)
     finish_reason: Optional[str] = None
     output_logprobs: List[Optional[float]] = field(default_factory=list)   # SamplingParams.logprobs requests
+    output_top_logprobs: List[Optional[list]] = field(default_factory=list)   # SamplingParams.top_logprobs requests
 
 
 def _engine_main(cfg: EngineConfig, device_index: Optional[int], req_conn, out_conn, warmup: bool) -> None:
@@ -120,8 +121,8 @@ def _engine_main(cfg: EngineConfig, device_index: Optional[int], req_conn, out_c
             if len(step_times) > 4096:
                 del step_times[:2048]
             if outs:
-                out_conn.send(("out", [(o.request_id, o.new_token_ids, o.finished, o.finish_reason, o.new_logprobs)
-                                      for o in outs]))
+                out_conn.send(("out", [(o.request_id, o.new_token_ids, o.finished, o.finish_reason, o.new_logprobs,
+                                        o.new_top_logprobs) for o in outs]))
     finally:
         if prof is not None:
             prof.disable()
@@ -198,7 +199,10 @@ class ProcessAsyncEngine:
             kind = msg[0]
             if kind == "out":
                 by_loop: Dict = {}
-                for rid, new_ids, finished, reason, new_lps in msg[1]:
+                for item in msg[1]:
+                    rid, new_ids, finished, reason, new_lps = item[:5]
+                    # top-N alternatives ride sixth; a five-field tuple (stub pipes) carries none
+                    new_tops = item[5] if len(item) > 5 else None
                     sink = self._sinks.get(rid)
                     if sink is None:
                         continue
@@ -207,10 +211,12 @@ class ProcessAsyncEngine:
                         seq.output_ids.extend(new_ids)
                         if new_lps is not None:
                             seq.output_logprobs.extend(new_lps)
+                        if new_tops is not None:
+                            seq.output_top_logprobs.extend(new_tops)
                         if finished:
                             seq.finish_reason = reason
                     by_loop.setdefault(sink[0], []).append((sink[1], StepOutput(rid, new_ids, finished, reason, seq,
-                                                                                new_lps)))
+                                                                                new_lps, new_tops)))
                 for loop, items in by_loop.items():
                     try:
                         loop.call_soon_threadsafe(_deliver, items)

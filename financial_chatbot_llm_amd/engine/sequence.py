@@ -6,7 +6,7 @@ import enum
 import itertools
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence as Seq
+from typing import List, Optional, Sequence as Seq, Tuple
 
 
 # Start of the user turn a request belongs to (time.perf_counter), set by the serving layer for
@@ -47,6 +47,12 @@ class SamplingParams:
     # temperature, top-k / top-p and the constraint choose the token, not the number.  Never changes a
     # token.  TP = 1 without CP only.
     logprobs: bool = False
+    # also report, per sampled token, the N most likely tokens of the same raw distribution with their
+    # log-probabilities (Sequence.output_top_logprobs, StepOutput.new_top_logprobs): 0 (off) .. 20,
+    # implies ``logprobs``.  Descending, equal logits by ascending token id; no mask, penalty or
+    # top-k / top-p applies.  Never changes a token; steps holding such a row pay one LM-head logits
+    # GEMM where they would sample inside the fused LM head.  TP = 1 without CP only.
+    top_logprobs: int = 0
     # penalties on tokens the sequence holds already (ops.penalty), applied to the logits in front of
     # the automaton mask, top-k / top-p and the sampler: repetition divides a positive (multiplies a
     # negative) logit of every token in the prompt or the output; presence is subtracted once and
@@ -85,6 +91,11 @@ class Sequence:
         # here.  A sampled token carries its log-probability, a token appended without a sample
         # (forced_output, jump-forward, grammar-forced) None.
         self.output_logprobs: List[Optional[float]] = []
+        # with params.top_logprobs > 0: parallel to output_logprobs, by the same alignment rules -- a
+        # sampled token carries its row's N (token id, log-probability) alternatives, a token appended
+        # without a sample None.  The sampled token's output_logprobs entry comes from the same row of
+        # logits: where the token is among its alternatives the two values are equal bit for bit.
+        self.output_top_logprobs: List[Optional[List[Tuple[int, float]]]] = []
         self.params = params
         self.status = SeqStatus.WAITING
         self.block_table: List[int] = []

@@ -13,7 +13,7 @@ from .retrieval import filtered_topk
 from .sampling import (apply_top_k_top_p, fused_lm_head_ok, fused_logprob_ok, lm_head_logprobs, lm_head_sample,
                        lm_head_sample_logprob, lm_head_sample_shard, lm_head_stream_sample,
                        lm_head_stream_sample_logprob, merge_logprob_stats, pick_pairs, sample, sample_shard,
-                       token_logprobs)
+                       token_logprobs, topn_logprobs)
 from .constrain import FsmTables, build_masks, sample_constrained
 from . import penalty
 from .penalty import PenaltyTable, apply_penalties

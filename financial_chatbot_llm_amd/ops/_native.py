@@ -89,6 +89,7 @@ _SIGS = {
                                             c_int, c_int, P],
     "penny_lm_sample_logprob_final": [P, P, P, P, P, c_int, c_int, P, P, P],
     "penny_token_logprob": [P, c_int, c_long, P, P, c_int, c_int, P],
+    "penny_topn_logprob": [P, c_int, c_long, P, P, c_int, P, P, P, c_int, c_int, P],
     "penny_sample_shard": [P, c_int, c_long, P, P, P, P, c_int, c_int, c_int, P],
     "penny_topk_topp_threshold": [P, c_int, c_long, P, P, P, P, c_int, c_int, P],
     "penny_moe_route": [P, c_int, c_int, c_int, P, P, P, P, P],

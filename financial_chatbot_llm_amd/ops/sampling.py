@@ -247,6 +247,84 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, out: Optional[torch.
     return out
 
 
+TOPN_MAX = 20  # alternatives per token the HIP kernel can report (sampler.hip TOPN_MAX)
+
+
+def _topn_ref(logits: torch.Tensor, ids: torch.Tensor, tn: torch.Tensor, lp: torch.Tensor, top_ids: torch.Tensor,
+              top_lp: torch.Tensor) -> None:
+    """The kernel's operation order in torch: the row's log-softmax once, the chosen token's value and
+    the alternatives read off it; a stable descending sort on the values (-0 folded into +0), so equal
+    logits keep ascending ids.  A row holding a NaN or +inf logit has NaN values throughout."""
+    lf = logits.float()
+    V = lf.shape[1]
+    chosen = _token_logprobs_ref(logits, ids)
+    lsm = torch.log_softmax(lf, -1)
+    order = torch.sort(lf + 0.0, dim=-1, descending=True, stable=True).indices     # -0 + 0 = +0
+    for b in range(lf.shape[0]):
+        n = int(tn[b])
+        if n <= 0:
+            continue
+        sel = order[b, :n]
+        lp[b] = chosen[b]
+        top_ids[b, :n] = sel.to(torch.int32)
+        top_lp[b, :n] = lsm[b, sel]
+
+
+def topn_logprobs(logits: torch.Tensor, ids: torch.Tensor, topn, out=None):
+    """Top-N alternatives per row: logits [B, V] bf16 or f32, ids [B] integer token ids, topn [B]
+    integers (or one integer for every row), 0 .. ``TOPN_MAX`` and at most V -> (logprob f32 [B],
+    top_ids int32 [B, TOPN_MAX], top_lp f32 [B, TOPN_MAX]).  Per row with n = topn[row] > 0: logprob is
+    ``token_logprobs(logits, ids)[row]`` bit for bit; top_ids[row, :n] are the n largest logits'
+    ids, descending, equal logits (+0 == -0) by ascending id; top_lp their log softmax over the raw
+    logits at temperature 1, by the chosen token's formula.  Rows with n <= 0 and columns >= n are not
+    written (``out``: the three tensors to fill; fresh ones are zeroed).  A NaN / +inf row reports NaN
+    values and unspecified ids in [0, V).  A ``topn`` tensor on the device is not read by the host (no
+    sync, graph-capturable): the kernel caps its rows at min(TOPN_MAX, V).  Anything else outside the
+    contract raises ValueError before any launch."""
+    if logits.dim() != 2:
+        raise ValueError(f"topn_logprobs takes [B, V] logits, got {tuple(logits.shape)}")
+    B, V = logits.shape
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"topn_logprobs takes bf16 or f32 logits, not {logits.dtype}")
+    if V <= 0:
+        raise ValueError("topn_logprobs: empty vocabulary")
+    if tuple(ids.shape) != (B,) or ids.dtype.is_floating_point:
+        raise ValueError(f"topn_logprobs: ids must be [B] = [{B}] integers, got {tuple(ids.shape)} {ids.dtype}")
+    dev = logits.device
+    if not torch.is_tensor(topn):
+        topn = torch.as_tensor(topn, dtype=torch.int32)
+        if topn.dim() == 0:
+            topn = topn.expand(B)
+    if tuple(topn.shape) != (B,) or topn.dtype.is_floating_point:
+        raise ValueError(f"topn_logprobs: topn must be [B] = [{B}] integers, got {tuple(topn.shape)} {topn.dtype}")
+    max_n = min(TOPN_MAX, V)
+    if topn.device.type == "cpu" and B:
+        hi = int(topn.max())
+        if hi > TOPN_MAX or hi > V:
+            bound = f"TOPN_MAX = {TOPN_MAX}" if hi > TOPN_MAX else f"V = {V}"
+            raise ValueError(f"topn_logprobs: n = {hi} exceeds {bound}")
+        max_n = max(hi, 0)
+    if out is None:
+        lp = torch.zeros((B,), dtype=torch.float32, device=dev)
+        top_ids = torch.zeros((B, TOPN_MAX), dtype=torch.int32, device=dev)
+        top_lp = torch.zeros((B, TOPN_MAX), dtype=torch.float32, device=dev)
+    else:
+        lp, top_ids, top_lp = out
+        for t, shape, dt in ((lp, (B,), torch.float32), (top_ids, (B, TOPN_MAX), torch.int32),
+                             (top_lp, (B, TOPN_MAX), torch.float32)):
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"topn_logprobs: out must be contiguous {shape} {dt} on {dev}")
+    if not N.use_native(logits):
+        _topn_ref(logits, ids.to(dev), topn.to(dev).clamp(max=max_n), lp, top_ids, top_lp)
+        return lp, top_ids, top_lp
+    logits = _aligned_rows(logits)
+    idc = ids.to(device=dev, dtype=torch.int32).contiguous()              # alive across the launch
+    tnc = topn.to(device=dev, dtype=torch.int32).contiguous()
+    N.call("penny_topn_logprob", N.ptr(logits), int(logits.dtype == torch.float32), logits.stride(0), N.ptr(idc),
+           N.ptr(tnc), int(max_n), N.ptr(lp), N.ptr(top_ids), N.ptr(top_lp), B, V, N.stream())
+    return lp, top_ids, top_lp
+
+
 def lm_head_stream_sample_logprob(h: torch.Tensor, w: torch.Tensor, temperatures: torch.Tensor, seeds: torch.Tensor,
                                   vvalid: Optional[int] = None, voff: int = 0, out: Optional[torch.Tensor] = None,
                                   logprob: Optional[torch.Tensor] = None, nf: Optional[int] = None,

@@ -42,6 +42,7 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
                          today_fn=today_fn, max_transaction_tokens=retrieval_limit_tokens(),
                          decide_logprobs=serving.decide_logprobs,
                          decide_confidence_threshold=serving.decide_confidence_threshold,
+                         decide_top_logprobs=serving.decide_top_logprobs,
                          respond_penalties=serving.respond_penalties())
     return Services(db=db, kafka=kafka, agent=agent, retrieval=retrieval, serving=serving)
 
@@ -77,6 +78,7 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
                          max_transaction_tokens=retrieval_cfg.max_limit_tokens,
                          decide_logprobs=serving.decide_logprobs,
                          decide_confidence_threshold=serving.decide_confidence_threshold,
+                         decide_top_logprobs=serving.decide_top_logprobs,
                          respond_penalties=serving.respond_penalties())
     return Services(db=db or Database(), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)

@@ -47,6 +47,10 @@ def parse(argv=None):
     ap.add_argument("--decide-logprobs", action="store_true",
                     default=os.environ.get("PENNY_DECIDE_LOGPROBS", "0").lower() in ("1", "true", "yes"),
                     help="record the decide call's confidence, exp(mean token log-probability), in the metrics")
+    ap.add_argument("--decide-top-logprobs", type=int, default=None, metavar="N",
+                    help="the decide call asks for N (2..20) alternatives per sampled token and records the first "
+                         "token's margin over the best other one in the metrics (default: "
+                         "PENNY_DECIDE_TOP_LOGPROBS, 0)")
     ap.add_argument("--constrain-toolcalls", action="store_true",
                     default=os.environ.get("PENNY_CONSTRAIN_TOOLCALLS", "0").lower() in ("1", "true", "yes"),
                     help="decide calls sample under the tool-call token automaton (TP = 1 only)")
@@ -103,6 +107,8 @@ def build_leader_services(args, engine, device):
                          max_transaction_tokens=retrieval_limit_tokens(),     # PENNY_MAX_TRANSACTION_TOKENS
                          decide_logprobs=args.decide_logprobs or serving.decide_logprobs,
                          decide_confidence_threshold=serving.decide_confidence_threshold,
+                         decide_top_logprobs=(serving.decide_top_logprobs if args.decide_top_logprobs is None
+                                              else args.decide_top_logprobs),
                          respond_penalties=serving.respond_penalties())
     broker = InMemoryBroker() if args.smoke else None
     return Services(db=Database(uri="" if args.smoke else None), kafka=KafkaClient(broker=broker), agent=agent,
