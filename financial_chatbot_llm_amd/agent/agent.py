@@ -61,11 +61,17 @@ class LLMAgent:
                  system_prompt: Optional[str] = None, tool_prompt: Optional[str] = None,
                  max_transaction_tokens: Optional[int] = config.MAX_TRANSACTION_TOKENS,
                  decide_logprobs: bool = False, decide_confidence_threshold: float = 0.5,
-                 decide_top_logprobs: int = 0, respond_penalties: Optional[Dict[str, float]] = None):
+                 decide_top_logprobs: int = 0, respond_penalties: Optional[Dict[str, float]] = None,
+                 decide_adapter: Optional[str] = None, respond_adapter: Optional[str] = None):
         self.llm = llm
+        # LoRA adapters the two calls ask the engine for (ServingConfig.decide_adapter / respond_adapter;
+        # None: the base model).  A scripted decide still runs the model, so under its adapter too
+        self.decide_adapter, self.respond_adapter = decide_adapter or None, respond_adapter or None
         # repetition_penalty / presence_penalty / frequency_penalty of the streamed respond call
         # (ServingConfig.respond_penalties); the decide call never gets them: its output is JSON
         self.respond_penalties: Dict[str, float] = dict(respond_penalties or {})
+        if self.respond_adapter:      # rides with the respond call's other keyword arguments
+            self.respond_penalties["adapter"] = self.respond_adapter
         # decide confidence (ServingConfig.decide_logprobs): the decide call asks for the sampled
         # tokens' log-probabilities and exp(mean) goes to the metrics registry
         self.decide_logprobs = bool(decide_logprobs)
@@ -150,6 +156,8 @@ class LLMAgent:
         extra = {"logprobs": True} if self.decide_logprobs else {}
         if self.decide_top_logprobs:
             extra["top_logprobs"] = self.decide_top_logprobs
+        if self.decide_adapter:
+            extra["adapter"] = self.decide_adapter
         result = await self.llm.agenerate(self.decide_messages(state), tools=self.bound_tools,
                                           temperature=self.temperature, max_tokens=self.max_decide_tokens,
                                           purpose="decide", ephemeral_kv=bool(state["tool_results"]), **extra)

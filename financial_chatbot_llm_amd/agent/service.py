@@ -25,9 +25,12 @@ logger = get_logger(__name__)
 class LLMService:
     def __init__(self, llm: LLMBackend, system_prompt: Optional[str] = None,
                  temperature: float = config.DEFAULT_TEMPERATURE, max_response_tokens: int = 512,
-                 respond_penalties: Optional[dict] = None):
+                 respond_penalties: Optional[dict] = None, respond_adapter: Optional[str] = None,
+                 decide_adapter: Optional[str] = None):
         self.llm = llm
         self.respond_penalties = dict(respond_penalties or {})     # ServingConfig.respond_penalties
+        if respond_adapter:       # the chain's one call runs on the respond adapter (there is no decide call)
+            self.respond_penalties["adapter"] = respond_adapter
         self.system_prompt = system_prompt if system_prompt is not None else _load_system_prompt()
         self.temperature = temperature
         self.max_response_tokens = max_response_tokens

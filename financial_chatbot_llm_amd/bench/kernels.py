@@ -924,6 +924,111 @@ def bench_topn_logprob(dev, Ms=(16, 64, 128, 256), Ns=(1, 5, 20), V: int = 12825
     return out
 
 
+def bench_lora(dev, Ms=(16, 64, 128, 256, 2048, 8192), ranks=(16, 64)) -> List[Dict]:
+    """Multi-LoRA (ops.lora) at the Llama-3-8B shapes -- QKV 6144 x 4096, O 4096 x 4096, down 4096 x 14336
+    -- per (projection, rank, M rows), variants interleaved in one process: (a) the base projection alone,
+    the ``linear`` call a LoRA step makes; (b) base + shrink + expand with every row on one adapter; (c)
+    the same with four adapters interleaved row by row; (d) the same with no adapter row (what a loaded
+    but idle table costs a step that still carries a row_slot).  ``floor_us`` is the delta's bytes-moved
+    floor at 6 TB/s: x read once, the output read and written, the used adapters' tables once.  Then the
+    step pair: the three projections of 32 layers as one captured graph at B = 64 / 128 with 0 / 50 /
+    100 % adapter rows against the same chain without the delta launches.  Each figure is the median of
+    the rounds with their min and max."""
+    from ..ops import gemm
+    from ..ops.gemm import Slabs
+    gemm.load_gemm_tuning("llama3-8b")
+    shapes = {"qkv": ((4096, 1024, 1024), 4096), "o": ((4096,), 4096), "down": ((4096,), 14336)}
+    out = []
+
+    def timed(fns, rounds=7, iters=20):
+        for f in fns.values():
+            f()
+        torch.cuda.synchronize()
+        res = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, f in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    f()
+                b.record()
+                b.synchronize()
+                res[k].append(a.elapsed_time(b) * 1e3 / iters)
+        return {k: (statistics.median(v), min(v), max(v)) for k, v in res.items()}
+
+    def fill(table, slots):
+        for s in range(slots):
+            t = {}
+            for g, (segs, K) in shapes.items():
+                for i, mod in enumerate(ops.lora.GROUPS[g]):
+                    t[(0, mod)] = (torch.randn((table.rank, K), device=dev) * 0.02, torch.randn((segs[i], table.rank), device=dev) * 0.02)
+            table.set(s, t, 2.0)
+
+    ws = {g: torch.randn((sum(segs), K), device=dev).to(torch.bfloat16) * 0.02 for g, (segs, K) in shapes.items()}
+    wts = {g: (gemm.tile_weight(w) if gemm.uses_tiled_weight(*w.shape) else None) for g, w in ws.items()}
+    for rank in ranks:
+        table = ops.LoRATable(4, rank, 1, shapes, dev)
+        fill(table, 4)
+        for g, (segs, K) in shapes.items():
+            N_ = sum(segs)
+            for M in Ms:
+                x = torch.randn((M, K), device=dev).to(torch.bfloat16)
+                slots = {"one": torch.zeros(M, dtype=torch.int32, device=dev),
+                         "four": (torch.arange(M, device=dev) % 4).to(torch.int32),
+                         "idle": torch.full((M,), -1, dtype=torch.int32, device=dev)}
+                base = lambda: gemm.linear(x, ws[g], wt=wts[g], slabs=True)      # noqa: E731
+                y0 = base()
+                f32 = isinstance(y0, Slabs)
+                fns = {"base": base}
+                for k, rs in slots.items():
+                    fns["lora_" + k] = (lambda rs=rs: ops.lora_delta(x, base(), table, 0, g, rs))
+                r = timed(fns, iters=20 if M <= 256 else 5)
+                row = {"op": "lora", "proj": g, "N": N_, "K": K, "R": rank, "M": M, "target": "slabs" if f32 else "bf16"}
+                for k, (med, lo, hi) in r.items():
+                    row[k + "_us"] = round(med, 1)
+                    row[k + "_spread_us"] = [round(lo, 1), round(hi, 1)]
+                tab = (len(segs) * table.R * K + N_ * table.R) * 2
+                for k, used in (("one", 1), ("four", min(4, M))):
+                    byt = M * K * 2 + 2 * M * N_ * (4 if f32 else 2) + used * tab
+                    row[f"floor_{k}_us"] = round(byt / 6e12 * 1e6, 1)
+                    row[f"price_{k}_us"] = round(r["lora_" + k][0] - r["base"][0], 1)
+                row["price_idle_us"] = round(r["lora_idle"][0] - r["base"][0], 1)
+                out.append(row)
+                print(json.dumps(row), flush=True)
+        # the step pair: 32 layers' projections under graph replay
+        for B in (64, 128):
+            xs = {g: torch.randn((B, K), device=dev).to(torch.bfloat16) for g, (_, K) in shapes.items()}
+            rs = torch.full((B,), -1, dtype=torch.int32, device=dev)
+
+            def chain(lora: bool):
+                for _ in range(32):
+                    for g in shapes:
+                        y = gemm.linear(xs[g], ws[g], wt=wts[g], slabs=True)
+                        if lora:
+                            ops.lora_delta(xs[g], y, table, 0, g, rs)
+            graphs = {}
+            for name, lora in (("default", False), ("lora", True)):
+                for _ in range(2):
+                    chain(lora)
+                torch.cuda.synchronize()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    chain(lora)
+                graphs[name] = gr
+            row = {"op": "lora_step", "B": B, "R": rank, "layers": 32}
+            for pct in (0, 50, 100):
+                rs.copy_(torch.where(torch.arange(B, device=dev) * 100 < pct * B,
+                                     (torch.arange(B, device=dev) % 4).to(torch.int32), torch.full_like(rs, -1)))
+                r = timed({"default": graphs["default"].replay, "lora": graphs["lora"].replay}, iters=10)
+                row[f"default_us_{pct}"] = round(r["default"][0], 1)
+                row[f"lora_us_{pct}"] = round(r["lora"][0], 1)
+                row[f"lora_spread_us_{pct}"] = [round(r["lora"][1], 1), round(r["lora"][2], 1)]
+                row[f"price_us_{pct}"] = round(r["lora"][0] - r["default"][0], 1)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+    return out
+
+
 def bench_bge_query(dev) -> List[Dict]:
     """bge-base encoder latency on retrieval-size query batches (the per-turn critical path): the
     four projections on hipBLASLt (+ the GELU pass) vs the tile kernel with the bias / bias+GELU
@@ -1971,6 +2076,7 @@ def main(argv=None) -> int:
                 "penalty_sample": bench_penalty_sample,
                 "lm_head_sample_logprob": bench_lm_head_sample_logprob,
                 "topn_logprob": bench_topn_logprob,
+                "lora": bench_lora,
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),

@@ -176,6 +176,11 @@ class EngineConfig:
     # once -- rows of the device count table, allocated at the first penalised request (2 bytes per
     # token and slot: 16.4 MB at V = 128256); further penalised requests queue for a slot
     penalty_slots: int = 64
+    # per-request LoRA adapters (ops.lora; Llama at TP = 1): adapters resident at once and their largest
+    # rank (at most 64; the device tables hold ranks zero-padded to a multiple of 32).  The tables are
+    # allocated at the first load_adapter: at Llama-3-8B with the default rank about 92 MB per slot
+    max_loras: int = 4
+    lora_max_rank: int = 16
 
     @classmethod
     def from_env(cls, **overrides) -> "EngineConfig":
@@ -213,6 +218,8 @@ class EngineConfig:
             device=_env("PENNY_DEVICE", cls.device),
             fsm_max_states=_env_int("PENNY_FSM_MAX_STATES", cls.fsm_max_states),
             penalty_slots=_env_int("PENNY_PENALTY_SLOTS", cls.penalty_slots),
+            max_loras=_env_int("PENNY_MAX_LORAS", cls.max_loras),
+            lora_max_rank=_env_int("PENNY_LORA_MAX_RANK", cls.lora_max_rank),
         )
         return dataclasses.replace(c, **overrides)
 
@@ -241,6 +248,22 @@ class RetrievalConfig:
             device=_env("PENNY_DEVICE", cls.device),
         )
         return dataclasses.replace(c, **overrides)
+
+
+def parse_lora_adapters(spec) -> Optional[dict]:
+    """``"name=/dir,name2=/dir2"`` (or a list of ``name=/dir``) -> ``{name: dir}``; None when empty."""
+    if not spec:
+        return None
+    out = {}
+    for item in (spec.split(",") if isinstance(spec, str) else list(spec)):
+        item = item.strip()
+        if not item:
+            continue
+        name, sep, path = item.partition("=")
+        if not sep or not name.strip() or not path.strip():
+            raise ValueError(f"LoRA adapter {item!r}: expected name=/directory")
+        out[name.strip()] = path.strip()
+    return out or None
 
 
 @dataclass
@@ -276,6 +299,12 @@ class ServingConfig:
     respond_repetition_penalty: float = 1.0
     respond_presence_penalty: float = 0.0
     respond_frequency_penalty: float = 0.0
+    # LoRA adapters loaded at start, ``{name: PEFT directory}`` (PENNY_LORA_ADAPTERS="name=/dir,name2=/dir2"),
+    # and the names the agent's decide and respond calls ask for (None: the base model); the legacy
+    # no-tools chain uses respond_adapter
+    lora_adapters: Optional[dict] = None
+    decide_adapter: Optional[str] = None
+    respond_adapter: Optional[str] = None
 
     def respond_penalties(self) -> dict:
         """The respond call's penalty keyword arguments: only those off their neutral value."""
@@ -283,6 +312,11 @@ class ServingConfig:
                 "presence_penalty": (self.respond_presence_penalty, 0.0),
                 "frequency_penalty": (self.respond_frequency_penalty, 0.0)}
         return {k: float(v) for k, (v, neutral) in vals.items() if float(v) != neutral}
+
+    def adapter_kwargs(self) -> dict:
+        """The agent's (or the legacy chain's) adapter keyword arguments: only those that are set."""
+        vals = {"decide_adapter": self.decide_adapter, "respond_adapter": self.respond_adapter}
+        return {k: v for k, v in vals.items() if v}
 
     @classmethod
     def from_env(cls, **overrides) -> "ServingConfig":
@@ -302,6 +336,9 @@ class ServingConfig:
             respond_repetition_penalty=_env_float("PENNY_RESPOND_REPETITION_PENALTY", cls.respond_repetition_penalty),
             respond_presence_penalty=_env_float("PENNY_RESPOND_PRESENCE_PENALTY", cls.respond_presence_penalty),
             respond_frequency_penalty=_env_float("PENNY_RESPOND_FREQUENCY_PENALTY", cls.respond_frequency_penalty),
+            lora_adapters=parse_lora_adapters(os.getenv("PENNY_LORA_ADAPTERS")),
+            decide_adapter=os.getenv("PENNY_DECIDE_ADAPTER") or None,
+            respond_adapter=os.getenv("PENNY_RESPOND_ADAPTER") or None,
         )
         return dataclasses.replace(c, **overrides)
 

@@ -8,7 +8,9 @@
 // newly full blocks, free on finish), so it is C++: O(1) allocation from a free stack, an
 // intrusive LRU list of evictable cached blocks, and an open hash map from chained block hashes
 // to block ids.  Cached blocks keep their token ids so a hash hit is VERIFIED against the actual
-// tokens (a collision can never alias two different prefixes' KV).
+// tokens (a collision can never alias two different prefixes' KV).  A sequence's chain starts at its
+// salt (0: the base model; each loaded LoRA adapter draws its own), which a cached block keeps and a
+// hit compares too: KV computed under one set of weights is never served to another.
 //
 // Block lifecycle: free -> owned (ref >= 1) -> [committed: hashed + cached] -> ref 0 ->
 // evictable (still cached, LRU) -> reclaimed when the free stack is empty.
@@ -41,6 +43,7 @@ struct Block {
   int ref = 0;
   uint64_t hash = 0;              // 0: not cached
   std::vector<int32_t> tokens;    // tokens of a cached block (verification)
+  uint64_t salt = 0;              // salt of the chain a cached block belongs to (verification)
   int lru_prev = -1, lru_next = -1;
   bool in_lru = false;
 };
@@ -48,6 +51,7 @@ struct Block {
 struct SeqState {
   std::vector<int> table;
   std::vector<uint64_t> hashes;   // chained hashes of committed full blocks
+  uint64_t salt = 0;              // where the sequence's hash chain starts (set by match_prefix)
 };
 
 class BlockAllocator {
@@ -74,19 +78,21 @@ class BlockAllocator {
   }
 
   // Attach cached full blocks of `tokens` (never the whole prompt: >= 1 token left to compute).
-  std::vector<int> match_prefix(int seq, const std::vector<int32_t>& tokens) {
+  // `salt` starts the sequence's hash chain, here and in its later commits; 0 gives the unsalted hashes.
+  std::vector<int> match_prefix(int seq, const std::vector<int32_t>& tokens, uint64_t salt = 0) {
     SeqState& s = seqs_[seq];
+    if (s.table.empty() && s.hashes.empty()) s.salt = salt;
     if (!caching_ || !s.table.empty()) return s.table;
     const int max_full = ((int)tokens.size() - 1) / bs_;
     queries_ += max_full;
-    uint64_t parent = 0;
+    uint64_t parent = s.salt;
     for (int i = 0; i < max_full; ++i) {
       const int32_t* t = tokens.data() + (size_t)i * bs_;
       const uint64_t h = block_hash(parent, t, bs_);
       auto it = cache_.find(h);
       if (it == cache_.end()) break;
       Block& blk = blocks_[it->second];
-      if (!std::equal(blk.tokens.begin(), blk.tokens.end(), t)) break;  // verified hit only
+      if (blk.salt != s.salt || !std::equal(blk.tokens.begin(), blk.tokens.end(), t)) break;  // verified hit only
       if (blk.ref == 0) lru_remove(it->second);
       blk.ref += 1;
       s.table.push_back(it->second);
@@ -122,7 +128,7 @@ class BlockAllocator {
     SeqState& s = it->second;
     const int nblocks = (int)tokens.size() / bs_;
     if (first_block != (int)s.hashes.size()) throw std::invalid_argument("commit out of order");
-    uint64_t parent = s.hashes.empty() ? 0 : s.hashes.back();
+    uint64_t parent = s.hashes.empty() ? s.salt : s.hashes.back();
     for (int i = 0; i < nblocks && first_block + i < (int)s.table.size(); ++i) {
       const int32_t* t = tokens.data() + (size_t)i * bs_;
       const uint64_t h = block_hash(parent, t, bs_);
@@ -132,6 +138,7 @@ class BlockAllocator {
         cache_[h] = b;
         blk.hash = h;
         blk.tokens.assign(t, t + bs_);
+        blk.salt = s.salt;
       }
       s.hashes.push_back(h);
       parent = h;

@@ -70,7 +70,7 @@ PYBIND11_MODULE(_penny_runtime, m) {
       .def("num_free", &BlockAllocator::num_free)
       .def("block_size", &BlockAllocator::block_size)
       .def("blocks_needed", &BlockAllocator::blocks_needed)
-      .def("match_prefix", &BlockAllocator::match_prefix)
+      .def("match_prefix", &BlockAllocator::match_prefix, py::arg("seq"), py::arg("tokens"), py::arg("salt") = 0)
       .def("grow", &BlockAllocator::grow)
       .def("commit", &BlockAllocator::commit)
       .def("num_committed", &BlockAllocator::num_committed)

@@ -52,7 +52,10 @@ class AsyncEngine:
         self._pending: List[Tuple[str, Seq[int], SamplingParams]] = []
         self._aborts: List[str] = []
         # score() calls: (token ids, caller's loop, its future), run by the engine thread between steps
-        self._scores: List[Tuple[List[int], asyncio.AbstractEventLoop, asyncio.Future]] = []
+        self._scores: List[Tuple[List[int], Optional[str], asyncio.AbstractEventLoop, asyncio.Future]] = []
+        # engine calls from other threads (load / unload / list adapters): (function of the engine, [event,
+        # result, error]), run by the engine thread between steps like score()
+        self._calls: List[Tuple[object, list]] = []
         self._sinks: Dict[str, Tuple[asyncio.AbstractEventLoop, asyncio.Queue]] = {}
         self._stop = False
         self.error: Optional[BaseException] = None
@@ -101,11 +104,18 @@ class AsyncEngine:
                 pending, self._pending = self._pending, []
                 aborts, self._aborts = self._aborts, []
                 scores, self._scores = self._scores, []
+                calls, self._calls = self._calls, []
             for rid in aborts:
                 eng.abort(rid)
-            for ids, loop, fut in scores:
+            for fn, w in calls:
                 try:
-                    res = eng.score(ids)
+                    w[1] = fn(eng)
+                except Exception as e:  # noqa: BLE001 - the caller raises it
+                    w[2] = e
+                w[0].set()
+            for ids, adapter, loop, fut in scores:
+                try:
+                    res = eng.score(ids, adapter=adapter)
                 except Exception as e:  # noqa: BLE001 - the caller's await raises it
                     res = e
                 try:
@@ -218,13 +228,36 @@ class AsyncEngine:
             last = o
         return last
 
-    async def score(self, prompt_ids: Seq[int]) -> ScoreResult:
+    def _call(self, fn):
+        """Run ``fn(engine)`` on the engine thread between two steps (directly while that thread is not
+        running) and return or raise what it did.  Blocks the calling thread."""
+        if not self._thread.is_alive() or threading.current_thread() is self._thread:
+            return fn(self.engine)
+        w = [threading.Event(), None, None]
+        with self._lock:
+            self._calls.append((fn, w))
+        self._wake.set()
+        w[0].wait()
+        if w[2] is not None:
+            raise w[2]
+        return w[1]
+
+    def load_adapter(self, name: str, path_or_state_dict, alpha: Optional[float] = None) -> int:
+        return self._call(lambda e: e.load_adapter(name, path_or_state_dict, alpha))
+
+    def unload_adapter(self, name: str) -> None:
+        return self._call(lambda e: e.unload_adapter(name))
+
+    def adapters(self) -> Dict[str, dict]:
+        return self._call(lambda e: e.adapters())
+
+    async def score(self, prompt_ids: Seq[int], adapter: Optional[str] = None) -> ScoreResult:
         """``LLMEngine.score`` from the event loop: queued like a submission and run by the engine
         thread between two steps, so it never races a step for the engine's state."""
         loop = asyncio.get_running_loop()
         fut: asyncio.Future = loop.create_future()
         with self._lock:
-            self._scores.append((list(prompt_ids), loop, fut))
+            self._scores.append((list(prompt_ids), adapter, loop, fut))
         self._wake.set()
         return await fut
 

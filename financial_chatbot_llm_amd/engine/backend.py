@@ -61,6 +61,7 @@ class EngineLLM(LLMBackend):
         self.constrain_tools = bool(constrain_tools) and self._can_constrain()
         self.fsm_max_states = fsm_max_states
         self._logprobs_ok: Optional[bool] = None     # decided (and warned about) at the first request
+        self._adapters_ok: Optional[bool] = None     # likewise, at the first request that names an adapter
         self._penalties_ok: Optional[bool] = None    # likewise
         self.respond_ignore_eos = respond_ignore_eos
         self.respond_tokens = respond_tokens
@@ -144,6 +145,22 @@ class EngineLLM(LLMBackend):
                                              "without CP; requests decode without them")
         return pen if self._penalties_ok else {}
 
+    def _adapter(self, kw) -> Optional[str]:
+        """The ``adapter`` keyword argument of a call.  ``LLMEngine`` refuses adapters on Mixtral and
+        under TP / CP; there the argument is dropped with one warning."""
+        name = kw.get("adapter") or None
+        if name is None:
+            return None
+        if self._adapters_ok is None:
+            core = getattr(self.engine, "engine", None)
+            arch = getattr(getattr(getattr(core, "model", None), "cfg", None), "arch", "llama")
+            self._adapters_ok = not self._parallel_engine() and arch == "llama"
+            if not self._adapters_ok:
+                from ..utils.logging import get_logger
+                get_logger(__name__).warning("LoRA adapters need a Llama engine at TP = 1 without CP; requests run "
+                                             "on the base model")
+        return name if self._adapters_ok else None
+
     def _constraint(self, tools):
         if not self.constrain_tools or not tools or self.decide_script is not None:
             return None
@@ -192,7 +209,7 @@ class EngineLLM(LLMBackend):
                                 ephemeral_kv=bool(kw.get("ephemeral_kv")),
                                 prompt_lookup=self.prompt_lookup, priority_ts=TURN_START.get(),
                                 logprobs=(bool(kw.get("logprobs")) and self._can_logprob()) or top_n > 0,
-                                top_logprobs=top_n, **self._penalties(kw))
+                                top_logprobs=top_n, adapter=self._adapter(kw), **self._penalties(kw))
         out = await self.engine.generate_all(ids, params)
         self._account(kw.get("purpose", "decide"), len(ids), out.seq)
         text = self.tok.decode(out.seq.output_ids)
@@ -207,7 +224,7 @@ class EngineLLM(LLMBackend):
         ids = self._encode(messages, None, n)
         params = SamplingParams(temperature=temperature, max_tokens=n, ignore_eos=self.respond_ignore_eos,
                                 ephemeral_kv=bool(kw.get("ephemeral_kv")), priority_ts=TURN_START.get(),
-                                **self._penalties(kw))
+                                adapter=self._adapter(kw), **self._penalties(kw))
         detok = IncrementalDetokenizer(self.tok)
         buf, k = [], 0
         async for o in self.engine.generate(ids, params):

@@ -74,7 +74,7 @@ class PyBlockManager:
         ids = seq.all_ids
         bs = self.block_size
         max_full = (len(ids) - 1) // bs
-        parent = 0
+        parent = getattr(seq, "cache_salt", 0)      # 0: the base model; an adapter's salt starts its own chains
         self.queries += max_full
         for i in range(max_full):
             h = block_hash(parent, ids[i * bs:(i + 1) * bs])
@@ -113,7 +113,7 @@ class PyBlockManager:
         if len(hashes) >= full:
             return
         ids = seq.all_ids
-        parent = hashes[-1] if hashes else 0
+        parent = hashes[-1] if hashes else getattr(seq, "cache_salt", 0)
         for i in range(len(hashes), full):
             h = block_hash(parent, ids[i * bs:(i + 1) * bs])
             b = seq.block_table[i]

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import secrets
 import time
 from collections import deque
 from dataclasses import dataclass
@@ -152,6 +153,9 @@ class LLMEngine:
         self.penalty_slots = max(1, int(getattr(cfg, "penalty_slots", 64)))
         self._pen_free: Optional[List[int]] = None        # allocated with the table
         self._pen_queue: deque = deque()
+        # LoRA adapters by name: {"slot", "salt", "info"}; a slot of the runner's table (allocated at the
+        # first load_adapter) belongs to one name from load_adapter to unload_adapter
+        self._adapters: Dict[str, dict] = {}
         self.timing = {"prepare_s": 0.0, "execute_s": 0.0, "post_s": 0.0}   # host-side step anatomy
         self.spec_stats = {"proposed": 0, "accepted": 0}   # prompt-lookup draft tokens
         self.scored_tokens = 0     # prompt tokens given a log-probability by score()
@@ -196,8 +200,11 @@ class LLMEngine:
             raise ValueError(f"top_logprobs must be an integer in 0..{TOPN_MAX}, got {tn!r}")
         if tn > self.model.cfg.vocab_size:
             raise ValueError(f"top_logprobs = {tn} exceeds the vocabulary of {self.model.cfg.vocab_size} tokens")
+        adapter = self._adapter_of(params.adapter)
         max_prompt = self.cfg.max_model_len - 1
         seq = Sequence(request_id, list(prompt_ids)[-max_prompt:], params)
+        if adapter is not None:
+            seq.lora_slot, seq.cache_salt = adapter["slot"], adapter["salt"]
         if params.constraint is not None:
             if self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None:
                 raise NotImplementedError("constrained decoding: TP / CP engines do not carry automaton states yet")
@@ -256,6 +263,80 @@ class LLMEngine:
     def has_work(self) -> bool:
         return (self.scheduler.has_work() or self._inflight is not None or bool(self.cp and self.cp.busy())
                 or bool(self._pen_queue))
+
+    # -- LoRA adapters -----------------------------------------------------------------------------
+    def _lora_supported(self) -> None:
+        if getattr(self.model.cfg, "arch", "") != "llama":
+            raise NotImplementedError(f"LoRA adapters: {self.model.cfg.arch} models are not supported (Llama only)")
+        if self.ps.tp_size > 1 or getattr(self.model, "tp_size", 1) > 1 or self.cp is not None \
+                or getattr(self.cfg, "cp_size", 1) > 1:
+            raise NotImplementedError("LoRA adapters: TP / CP engines do not carry per-row adapter slots yet")
+
+    def _adapter_of(self, name: Optional[str]) -> Optional[dict]:
+        """The loaded adapter a request or score() names (None: the base model)."""
+        if name is None:
+            return None
+        self._lora_supported()
+        if name not in self._adapters:
+            raise KeyError(f"no LoRA adapter named {name!r} is loaded (loaded: {sorted(self._adapters)})")
+        return self._adapters[name]
+
+    def load_adapter(self, name: str, path_or_state_dict, alpha: Optional[float] = None) -> int:
+        """Load a LoRA adapter (a PEFT directory, or a PEFT-named state dict) under ``name`` and return
+        its slot.  Loading a name again replaces it in its slot -- refused while a live request uses
+        it -- under a fresh prefix-cache salt, so KV computed under the old weights is never hit again.
+        Call it between ``step()``s on the thread that owns the engine."""
+        from ..models.lora import read_adapter
+        self._lora_supported()
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"adapter name {name!r}")
+        max_rank = int(getattr(self.cfg, "lora_max_rank", 16))
+        tensors, scale, info = read_adapter(path_or_state_dict, max_rank, alpha)
+        old = self._adapters.get(name)
+        if old is not None:
+            self._adapter_idle(name, old["slot"], "reload")
+            slot = old["slot"]
+        else:
+            used = {a["slot"] for a in self._adapters.values()}
+            free = [s for s in range(int(getattr(self.cfg, "max_loras", 4))) if s not in used]
+            if not free:
+                raise RuntimeError(f"all {len(used)} LoRA slots are in use (max_loras); unload an adapter first")
+            slot = free[0]
+        table = self.runner.ensure_lora_table(int(getattr(self.cfg, "max_loras", 4)), max_rank)
+        self._sync_device()
+        table.set(slot, tensors, scale)          # checks every shape against the model before it writes
+        salt = 0
+        while salt == 0 or any(a["salt"] == salt for a in self._adapters.values()):
+            salt = secrets.randbits(64)
+        self._adapters[name] = {"slot": slot, "salt": salt, "info": info}
+        logger.info(f"LoRA adapter {name!r} in slot {slot}: r={info['r']} scale={scale:g} "
+                    f"targets={info['target_modules']}")
+        return slot
+
+    def _adapter_idle(self, name: str, slot: int, what: str) -> None:
+        live = [s.request_id for s in self.requests.values() if not s.finished and s.lora_slot == slot]
+        if live:
+            raise RuntimeError(f"cannot {what} LoRA adapter {name!r}: {len(live)} live request(s) use it "
+                               f"(first: {live[0]})")
+
+    def _sync_device(self) -> None:
+        """The table is about to change: the step on the GPU (overlap mode) reads it."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
+    def unload_adapter(self, name: str) -> None:
+        """Free ``name``'s slot; refused while a live request uses it.  Its cached KV dies by LRU."""
+        if name not in self._adapters:
+            raise KeyError(f"no LoRA adapter named {name!r} is loaded")
+        a = self._adapters[name]
+        self._adapter_idle(name, a["slot"], "unload")
+        self._sync_device()
+        self.runner.lora_table.clear(a["slot"])
+        del self._adapters[name]
+
+    def adapters(self) -> Dict[str, dict]:
+        """``{name: {"slot", "r", "lora_alpha", "scale", "target_modules"}}`` of the loaded adapters."""
+        return {n: {"slot": a["slot"], **a["info"]} for n, a in self._adapters.items()}
 
     # -- penalty slots -----------------------------------------------------------------------------
     def _pen_take(self, seq: Sequence) -> bool:
@@ -690,7 +771,7 @@ class LLMEngine:
         t1 = t0
         if not batch.empty():
             with marker("engine.inputs"):
-                si = build_step_inputs(batch)
+                si = build_step_inputs(batch, lora=bool(self._adapters))
             if self.ps.tp_size > 1:
                 tb = time.perf_counter()
                 comm.broadcast_step(si)
@@ -727,7 +808,7 @@ class LLMEngine:
         batch = self.scheduler.schedule()
         if batch.empty():
             return []
-        si = build_step_inputs(batch)
+        si = build_step_inputs(batch, lora=bool(self._adapters))
         if self.ps.tp_size > 1:
             comm.broadcast_step(si)
         t1 = time.perf_counter()
@@ -855,13 +936,15 @@ class LLMEngine:
             self.step()
         return [s.output_ids for s in seqs]
 
-    def score(self, prompt_ids: Seq[int]) -> ScoreResult:
+    def score(self, prompt_ids: Seq[int], adapter: Optional[str] = None) -> ScoreResult:
         """Log-likelihood of a token sequence under the model, on the serving kernels: for each of the
         n - 1 next-token positions, log p(prompt_ids[i + 1] | prompt_ids[:i + 1]) (temperature 1,
         bf16-rounded logits) and whether that token is the argmax.  Synchronous; call it between
         ``step()``s on the thread that owns the engine.  The prompt runs as prefill chunks of at most
         ``max_num_batched_tokens`` rows on KV blocks borrowed for the call: no prefix-cache lookup
-        (every row is computed) and nothing committed to the cache; the blocks go back on return."""
+        (every row is computed) and nothing committed to the cache; the blocks go back on return.
+        ``adapter``: score under that loaded LoRA adapter (KeyError for an unknown name)."""
+        ad = self._adapter_of(adapter)
         ids = list(prompt_ids)
         if len(ids) < 2:
             raise ValueError("score() needs at least 2 tokens")
@@ -871,6 +954,8 @@ class LLMEngine:
             raise NotImplementedError("score(): TP / CP engines do not broadcast scoring steps yet")
         rows = len(ids) - 1                 # the last token is only ever a target
         seq = Sequence(f"score-{id(ids)}", ids[:rows], SamplingParams(temperature=0.0, max_tokens=1))
+        if ad is not None:
+            seq.lora_slot, seq.cache_salt = ad["slot"], ad["salt"]
         if not self.bm.grow(seq, rows):
             raise RuntimeError(f"score(): {self.bm.blocks_needed(seq, rows)} KV blocks needed, "
                                f"{self.bm.num_free()} free")
@@ -899,6 +984,9 @@ class LLMEngine:
                 "penalty_steps": self.runner.stats["penalty_steps"],
                 "penalty_rows": self.runner.stats["penalty_rows"],
                 "penalty_waiting": len(self._pen_queue),
+                "lora_steps": self.runner.stats["lora_steps"], "lora_rows": self.runner.stats["lora_rows"],
+                "lora_slots_used": len(self._adapters),
+                "lora_table_mb": round(self.runner.lora_table.num_bytes() / 1e6, 1) if self.runner.lora_table else 0.0,
                 "kv_dtype": self.kv.kv_dtype,
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),

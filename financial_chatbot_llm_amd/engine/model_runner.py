@@ -78,6 +78,11 @@ class StepInputs:
     # asks).  Such a step samples as it would without them, then reads the alternatives -- and those
     # rows' log-probabilities -- off the step's raw logits (``ModelRunner._sample``).  Not on the C4 wire.
     topn: Optional[np.ndarray] = None
+    # [T] int32 LoRA table slot per row (SamplingParams.adapter; -1: the base model; None: no row of the
+    # step has one): every row of a sequence -- prompt chunks, known and jump-forward runs, prompt-lookup
+    # verification rows, decode rows -- carries its sequence's slot.  Not on the C4 wire: TP / CP
+    # engines refuse the request.
+    row_slot: Optional[np.ndarray] = None
 
     @property
     def num_prefill_tokens(self) -> int:
@@ -86,7 +91,7 @@ class StepInputs:
     # -- C4 wire format: one flat byte buffer (no pickling) ------------------------------------
     _ARRAYS = ("ids", "positions", "slots", "cu_q", "ctx_p", "bt_p", "ctx_d", "bt_d", "logits_idx", "temps",
                "seeds", "top_k", "top_p", "src", "pwork", "fsm_state")
-    _LOCAL = ("pen", "pen_params", "pen_add", "topn")     # staged with the step's arrays, never sent
+    _LOCAL = ("pen", "pen_params", "pen_add", "topn", "row_slot")     # staged with the step's arrays, never sent
 
     def pack(self) -> np.ndarray:
         """[header int64: max_q_len, then (dtype code, rows, cols) per array] + raw array bytes."""
@@ -219,9 +224,10 @@ def _table(rows: List[List[int]]) -> np.ndarray:
     return out
 
 
-def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
+def build_step_inputs(batch: ScheduledBatch, lora: bool = False) -> StepInputs:
     """The host arrays of one step.  Per-token work is numpy (a prefill step carries ~2-4k tokens:
-    a per-token Python list build cost ~1 ms of the host's critical path between GPU steps)."""
+    a per-token Python list build cost ~1 ms of the host's critical path between GPU steps).
+    ``lora``: the engine holds adapters, so the rows' slots are collected (``StepInputs.row_slot``)."""
     ids_parts: List[np.ndarray] = []
     pos_parts: List[np.ndarray] = []
     slot_parts: List[np.ndarray] = []
@@ -231,7 +237,10 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     want_lp = want_tn = False
     pen = _PenRows()
     max_q = 0
+    rs_parts: List[np.ndarray] = []
     for seq, start, n in batch.prefill:
+        if lora:
+            rs_parts.append(np.full(n, seq.lora_slot, np.int32))
         np_ = len(seq.prompt_ids)
         if start + n <= np_:
             ids_parts.append(np.asarray(seq.prompt_ids[start:start + n], np.int32))
@@ -289,6 +298,10 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
     i32 = lambda x: np.asarray(x, np.int32)  # noqa: E731
     cat = lambda parts, tail: np.concatenate(parts + [i32(tail)]) if parts else i32(tail)  # noqa: E731
     src_a = i32(src) if any(x >= 0 for x in src) else None
+    row_slot = None
+    if lora:
+        row_slot = cat(rs_parts, [seq.lora_slot for seq in batch.decode])
+        row_slot = row_slot if bool((row_slot >= 0).any()) else None
     bt_d = _table(tables_d)
     if _attn.LEAN_FLAGS & 1 and _attn.DECODE_LEAN and len(ctx_d) >= _attn.LEAN_NT_MIN_B:
         # the lean kernel's cache policy per block -- only where ops.decode keeps the NT bit
@@ -297,7 +310,7 @@ def build_step_inputs(batch: ScheduledBatch) -> StepInputs:
                       _table(tables_p), max_q, i32(ctx_d), bt_d, np.asarray(logits_idx, np.int64),
                       np.asarray(temps, np.float32), np.asarray(seeds, np.int64), i32(tk), np.asarray(tp, np.float32),
                       src_a, None, i32(fsm) if any(x != -1 for x in fsm) else None, bool(want_lp), *pen.arrays(),
-                      i32(tn) if want_tn else None)
+                      i32(tn) if want_tn else None, row_slot)
 
 
 def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
@@ -310,7 +323,8 @@ def prefill_step_inputs(seq: Sequence, start: int, n: int) -> StepInputs:
     return StepInputs(np.asarray(seq.prompt_ids[start:start + n], np.int32), p, bt[p // KV_BS] * KV_BS + p % KV_BS,
                       np.asarray([0, n], np.int32), np.asarray([start + n], np.int32), _table([seq.block_table]), n,
                       e, _table([]), np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros(0, np.int64), e,
-                      np.zeros(0, np.float32), None)
+                      np.zeros(0, np.float32), None,
+                      row_slot=np.full(n, seq.lora_slot, np.int32) if seq.lora_slot >= 0 else None)
 
 
 class CollectiveTimeout(RuntimeError):
@@ -424,24 +438,29 @@ def default_graph_kind(shard: bool, fused: bool) -> str:
 
 DEFAULT_GRAPH, EAGER = "default", "eager"
 TOPN_TWIN = "+topn"      # suffix of a twin's sampler name: the same sampling stage, then the alternatives
+LORA_TWIN = "+lora"      # last suffix of a twin's sampler name: the same graph with the rows' adapter deltas
 
 
 def graph_plan(fsm: bool, filters: bool, lp: bool, bucket_fused: bool, tp: bool, pen: bool = False,
-               topn: bool = False):
+               topn: bool = False, lora: bool = False):
     """What runs a pure-decode step whose bucket's default graph is ``bucket_fused`` or not:
     DEFAULT_GRAPH, EAGER, or the (sampler, lp) of the bucket's twin graph, captured on the first step
     that needs it.  The default graph has no automaton, no penalties, no log-probabilities and, when
     fused, no top-k / top-p; twins exist at TP = 1 only, and none holds penalties and the automaton
     together (such a step runs eagerly).  ``topn`` (a row asks for alternatives, which implies ``lp``)
     picks the twin the step would replay without it, with ``TOPN_TWIN`` appended to the sampler's name:
-    a graph of its own, so the plain twins stay as they are."""
+    a graph of its own, so the plain twins stay as they are.  ``lora`` (a row runs on an adapter):
+    whatever graph the step would replay without it -- the default graph included -- has a twin of its
+    own with ``LORA_TWIN`` appended last; what runs eagerly without it still does."""
     lp = lp or topn
     if not (fsm or pen or lp or (filters and bucket_fused)):
-        return DEFAULT_GRAPH
+        if not lora:
+            return DEFAULT_GRAPH
+        return EAGER if tp else (("fused" if bucket_fused else "logits") + LORA_TWIN, False)
     if tp or (fsm and pen):
         return EAGER
     kind = "fsm" if fsm else "pen" if pen else "logits" if filters or not bucket_fused else "fused"
-    return kind + (TOPN_TWIN if topn else ""), lp
+    return kind + (TOPN_TWIN if topn else "") + (LORA_TWIN if lora else ""), lp
 
 
 class ModelRunner:
@@ -485,13 +504,17 @@ class ModelRunner:
         self.pen_table: Optional[ops.PenaltyTable] = None
         self._pen_static = None
         self._topn_static = None                          # per-row N of the top-N graph twins
+        # LoRA (ops.lora): the adapter table, allocated by the engine at the first load_adapter
+        # (``ensure_lora_table``) and handed to the model with a step's row slots, and the per-row slots of the LoRA graph twins
+        self.lora_table: Optional[ops.LoRATable] = None
+        self._lora_static = None
         self._static = None
         self.graph_pool = None
         self.stats = {"steps": 0, "graph_steps": 0, "tokens": 0, "prefill_steps": 0, "prefill_step_tokens": 0,
                       "prefill_tile_pad_rows": 0, "prefill_m_hist": [0] * len(PREFILL_M_BUCKETS), "gpu_graph_s": 0.0, "gpu_eager_s": 0.0,
                       "gpu_idle_s": 0.0, "gpu_idle_gaps": 0, "_prev_end_ev": None, "overlap_steps": 0,
                       "constrained_steps": 0, "constrained_tokens": 0, "logprob_steps": 0,
-                      "penalty_steps": 0, "penalty_rows": 0, "top_logprob_steps": 0}
+                      "penalty_steps": 0, "penalty_rows": 0, "top_logprob_steps": 0, "lora_steps": 0, "lora_rows": 0}
         # TP prefill steps of >= overlap_min_rows rows run as two micro-batches whose all-reduces
         # overlap the other half's compute (PENNY_TP_OVERLAP=0 disables)
         self.tp_overlap = os.environ.get("PENNY_TP_OVERLAP", "1") == "1"
@@ -587,6 +610,8 @@ class ModelRunner:
         if si.num_decode:
             m.ctx_lens_d = self._to_dev(si.ctx_d)
             m.block_tables_d = self._to_dev(si.bt_d)
+        if si.row_slot is not None:
+            m.row_slot, m.lora = self._to_dev(si.row_slot), self.lora_table
         return m
 
     def register_automaton(self, a) -> int:
@@ -624,6 +649,23 @@ class ModelRunner:
             logger.info(f"penalty table: {slots} slots x {self.pen_table.Vs} tokens "
                         f"({self.pen_table.table.numel() * 2 / 1e6:.1f} MB)")
         return self.pen_table
+
+    def ensure_lora_table(self, slots: int, max_rank: int) -> "ops.LoRATable":
+        """The adapter table of the model's QKV / O / down projections, allocated at the first call: the
+        LoRA graph twins capture its pointers, so it is never replaced."""
+        if self.lora_table is None:
+            m, c = self.model, self.model.cfg
+            shapes = {"qkv": ((m.hq * m.D, m.hkv * m.D, m.hkv * m.D), c.hidden_size),
+                      "o": ((c.hidden_size,), m.hq * m.D), "down": ((c.hidden_size,), c.intermediate_size)}
+            self.lora_table = ops.LoRATable(slots, max_rank, c.num_layers, shapes, self.device,
+                                            dtype=getattr(m, "dtype", torch.bfloat16))
+            logger.info(f"LoRA table: {slots} slots x rank {self.lora_table.R} "
+                        f"({self.lora_table.bytes_per_slot() / 1e6:.1f} MB per slot)")
+        return self.lora_table
+
+    def _count_lora_step(self, si: StepInputs) -> None:
+        self.stats["lora_steps"] += 1
+        self.stats["lora_rows"] += int((si.row_slot >= 0).sum())
 
     def _resolve_pending_tok(self, row: torch.Tensor) -> torch.Tensor:
         """Pending rows (of the previous step's sampled vector, -1: none) -> the tokens they hold, read
@@ -863,6 +905,8 @@ class ModelRunner:
             self.stats["top_logprob_steps"] += 1
         if si.pen is not None:
             self._count_penalty_step(si)
+        if si.row_slot is not None:
+            self._count_lora_step(si)
         if si.fsm_state is not None:
             self.last_fsm_state[:n].copy_(so[:n], non_blocking=True)
             self.stats["constrained_steps"] += 1
@@ -913,6 +957,8 @@ class ModelRunner:
         if si.num_decode or si.src is not None or len(si.logits_idx):
             raise ValueError("score_chunk takes a prefill-only step without sampled rows")
         rows = np.flatnonzero(np.asarray(targets) >= 0)
+        if si.row_slot is not None:
+            self._count_lora_step(si)
         if si.pwork is None and self.on_gpu:
             si.pwork = prefill_plan(si.cu_q, si.ctx_p, self.G, self.model.hkv)
         self._stage_inputs(si)
@@ -1000,7 +1046,9 @@ class ModelRunner:
         """One decode step of bucket B on the static inputs, sampled by ``kind`` (None: the bucket's
         default sampler, decided here and returned)."""
         s = self._static
-        topn = None
+        topn = row_slot = None
+        if kind is not None and kind.endswith(LORA_TWIN):
+            kind, row_slot = kind[:-len(LORA_TWIN)], self._lora_static["slot"][:B]
         if kind is not None and kind.endswith(TOPN_TWIN):
             kind, topn = kind[:-len(TOPN_TWIN)], self._topn_static["n"][:B]
         fsm = kind == "fsm"
@@ -1021,7 +1069,8 @@ class ModelRunner:
             h = self.model.forward_decode_dual(s["ids"][:B], s["pos"][:B], metas, k, self.kv)
         else:
             meta = AttentionMetadata(slots=s["slots"][:B], num_prefill_tokens=0, num_decode=B,
-                                     ctx_lens_d=s["ctx"][:B], block_tables_d=s["bt"][:B], decode_ws=self.decode_ws)
+                                     ctx_lens_d=s["ctx"][:B], block_tables_d=s["bt"][:B], decode_ws=self.decode_ws,
+                                     row_slot=row_slot, lora=self.lora_table)
             h = self.model.forward(s["ids"][:B], s["pos"][:B], meta, self.kv)
         if kind is None:
             kind = default_graph_kind(self._shard_sampling(), self._fused_sampling(h))
@@ -1063,7 +1112,8 @@ class ModelRunner:
         B = self._bucket(si.num_decode)
         G = self.graphs[B]
         plan = graph_plan(si.fsm_state is not None, self._has_filters(si), si.want_logprobs, G.fused,
-                          getattr(self.model, "tp_size", 1) > 1, si.pen is not None, si.topn is not None)
+                          getattr(self.model, "tp_size", 1) > 1, si.pen is not None, si.topn is not None,
+                          si.row_slot is not None)
         if plan == DEFAULT_GRAPH:
             return G
         if plan == EAGER:
@@ -1088,6 +1138,9 @@ class ModelRunner:
         are restored after."""
         B, kind, lp = key
         s = self._static
+        if kind.endswith(LORA_TWIN):
+            self._alloc_lora_static()      # no row on an adapter (slot -1) until the replay fills them in
+            kind = kind[:-len(LORA_TWIN)]
         if kind.endswith(TOPN_TWIN):
             self._alloc_topn_static()      # no row asks (N = 0) until the replay fills them in
             kind = kind[:-len(TOPN_TWIN)]
@@ -1131,6 +1184,25 @@ class ModelRunner:
                                  "pinned": [torch.zeros(B, dtype=torch.int32).pin_memory() for _ in range(2)],
                                  "flip": 0}
         self._topn_static["n"].zero_()
+
+    def _alloc_lora_static(self) -> None:
+        """Static per-row adapter slots of the LoRA twins ([B] int32, one pinned copy per such graph
+        step), allocated with the first of them."""
+        B = self.max_decode_batch
+        if self._lora_static is None:
+            self._lora_static = {"slot": torch.full((B,), -1, dtype=torch.int32, device=self.device),
+                                 "pinned": [torch.zeros(B, dtype=torch.int32).pin_memory() for _ in range(2)],
+                                 "flip": 0}
+        self._lora_static["slot"].fill_(-1)
+
+    def _stage_lora_static(self, si: StepInputs, B: int) -> None:
+        ls = self._lora_static
+        pin = ls["pinned"][ls["flip"]]
+        ls["flip"] ^= 1
+        a = pin.numpy()
+        a[:B] = -1
+        a[:si.num_decode] = si.row_slot
+        ls["slot"].copy_(pin, non_blocking=True)
 
     def _stage_topn_static(self, si: StepInputs, B: int) -> None:
         ts = self._topn_static
@@ -1203,6 +1275,8 @@ class ModelRunner:
             self._stage_pen_static(si, B)
         if si.topn is not None:            # likewise a top-N twin
             self._stage_topn_static(si, B)
+        if si.row_slot is not None:        # likewise a LoRA twin
+            self._stage_lora_static(si, B)
         G.graph.replay()
         self.stats["graph_steps"] += 1
         return Sampled(G.out[:n], G.state_out, G.logprob, G.top_ids, G.top_lp)

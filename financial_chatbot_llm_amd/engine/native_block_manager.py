@@ -47,7 +47,7 @@ class NativeBlockManager:
     def match_prefix(self, seq: Sequence) -> int:
         if seq.block_table:
             return 0
-        seq.block_table = list(self.core.match_prefix(seq.seq_id, seq.all_ids))
+        seq.block_table = list(self.core.match_prefix(seq.seq_id, seq.all_ids, getattr(seq, "cache_salt", 0)))
         seq.num_computed = len(seq.block_table) * self.block_size
         seq.num_cached_prompt = seq.num_computed
         return seq.num_computed

@@ -40,7 +40,9 @@ from .sequence import SamplingParams
 
 logger = get_logger(__name__)
 _rid = itertools.count()
-_SCORE_ERRORS = {"ValueError": ValueError, "NotImplementedError": NotImplementedError, "RuntimeError": RuntimeError}
+_SCORE_ERRORS = {"ValueError": ValueError, "NotImplementedError": NotImplementedError, "RuntimeError": RuntimeError,
+                 "KeyError": KeyError, "FileNotFoundError": FileNotFoundError}
+_CALLS = ("load_adapter", "unload_adapter", "adapters")      # LLMEngine methods callable across the boundary
 
 
 @dataclass
@@ -93,10 +95,17 @@ def _engine_main(cfg: EngineConfig, device_index: Optional[int], req_conn, out_c
                     eng.abort(msg[1])
                 elif kind == "score":     # between two steps, like every control message
                     try:
-                        res = eng.score(msg[2])
+                        res = eng.score(msg[2], adapter=msg[3] if len(msg) > 3 else None)
                         out_conn.send(("score", msg[1], (res.logprobs, res.top1_match), None))
                     except Exception as e:  # noqa: BLE001 - raised again in the caller
                         out_conn.send(("score", msg[1], None, (type(e).__name__, str(e))))
+                elif kind == "call":      # load / unload / list adapters, between two steps
+                    try:
+                        if msg[2] not in _CALLS:
+                            raise ValueError(f"unknown engine call {msg[2]!r}")
+                        out_conn.send(("call", msg[1], getattr(eng, msg[2])(*msg[3]), None))
+                    except Exception as e:  # noqa: BLE001 - raised again in the caller
+                        out_conn.send(("call", msg[1], None, (type(e).__name__, str(e))))
                 elif kind == "stats":
                     s = eng.stats()
                     if step_times:
@@ -164,6 +173,7 @@ class ProcessAsyncEngine:
         self._score_waiters: Dict[int, Tuple[asyncio.AbstractEventLoop, asyncio.Future]] = {}
         self._stats_evt = threading.Event()
         self._stats: Dict[str, float] = {}
+        self._call_waiters: Dict[int, list] = {}       # call id -> [event, result, error]
         self.error: Optional[BaseException] = None
         self._closed = False
         t0 = time.perf_counter()
@@ -233,6 +243,11 @@ class ProcessAsyncEngine:
                         waiter[0].call_soon_threadsafe(_resolve, waiter[1], res)
                     except RuntimeError:
                         pass
+            elif kind == "call":
+                w = self._call_waiters.get(msg[1])
+                if w is not None:
+                    w[1], w[2] = msg[2], msg[3]
+                    w[0].set()
             elif kind == "stats":
                 self._stats = msg[1]
                 self._stats_evt.set()
@@ -264,6 +279,9 @@ class ProcessAsyncEngine:
                 loop.call_soon_threadsafe(_resolve, fut, err)
             except RuntimeError:
                 pass
+        for w in list(self._call_waiters.values()):
+            w[2] = ("RuntimeError", str(err))
+            w[0].set()
 
     def _send(self, msg) -> None:
         with self._send_lock:
@@ -300,14 +318,39 @@ class ProcessAsyncEngine:
             last = o
         return last
 
-    async def score(self, prompt_ids: Seq[int]) -> ScoreResult:
+    def _call(self, method: str, *args, timeout_s: float = 300.0):
+        """Run an ``LLMEngine`` method of ``_CALLS`` in the child between two of its steps and return
+        (or raise) what it did.  Blocks the calling thread."""
+        cid = next(_rid)
+        w = [threading.Event(), None, None]
+        self._call_waiters[cid] = w
+        try:
+            self._send(("call", cid, method, args))
+            if not w[0].wait(timeout_s):
+                raise TimeoutError(f"engine process did not answer {method} within {timeout_s:.0f}s")
+        finally:
+            self._call_waiters.pop(cid, None)
+        if w[2] is not None:
+            raise _SCORE_ERRORS.get(w[2][0], RuntimeError)(w[2][1])
+        return w[1]
+
+    def load_adapter(self, name: str, path_or_state_dict, alpha: Optional[float] = None) -> int:
+        return self._call("load_adapter", name, path_or_state_dict, alpha)
+
+    def unload_adapter(self, name: str) -> None:
+        return self._call("unload_adapter", name)
+
+    def adapters(self) -> Dict[str, dict]:
+        return self._call("adapters")
+
+    async def score(self, prompt_ids: Seq[int], adapter: Optional[str] = None) -> ScoreResult:
         """``LLMEngine.score`` in the child, between two of its steps."""
         loop = asyncio.get_running_loop()
         fut: asyncio.Future = loop.create_future()
         sid = next(_rid)
         self._score_waiters[sid] = (loop, fut)
         try:
-            self._send(("score", sid, list(prompt_ids)))
+            self._send(("score", sid, list(prompt_ids), adapter))
             return await fut
         finally:
             self._score_waiters.pop(sid, None)

@@ -63,6 +63,10 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # the LoRA adapter the request runs on, by the name it was loaded under (LLMEngine.load_adapter);
+    # None: the base model.  Rows of different adapters and of none share a step.  Llama at TP = 1
+    # without CP only.
+    adapter: Optional[str] = None
 
 
 class SeqStatus(enum.Enum):
@@ -137,6 +141,11 @@ class Sequence:
         self.pen_slot = -1
         self.pen_held = False
         self.pen_counted = 0
+        # LoRA: lora_slot -- the adapter's slot of the engine's table (-1: the base model), carried by every
+        # row of the sequence; cache_salt -- where the sequence's prefix-cache hash chain starts (0: the
+        # base model; an adapter's salt, so its KV is shared with requests on the same load of it only)
+        self.lora_slot = -1
+        self.cache_salt = 0
 
     def fsm_state_before(self, k: int) -> int:
         """Local automaton state in front of output token k (every earlier token known; -1: the

@@ -28,6 +28,8 @@ class AttentionMetadata:
     causal: bool = True
     prefill_work: Optional[torch.Tensor] = None  # [n, 2] int32 (ops.attention.prefill_work_list) or lean [., 6]
     prefill_lean: Optional[tuple] = None          # lean list counts (items, merges, slots), host ints
+    row_slot: Optional[torch.Tensor] = None       # [T] int32 LoRA table slot per row (-1: base model); None: no row has one
+    lora: Optional[object] = None                 # the ops.LoRATable those slots index (None: the model's own)
 
 
 class KVCache:

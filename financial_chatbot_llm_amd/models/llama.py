@@ -81,6 +81,9 @@ class DecoderModel:
         # sp_min_tokens rows run forward_sp (reduce-scatter / all-gather instead of all-reduce)
         self.sequence_parallel = False
         self.sp_min_tokens = 1024
+        # per-request LoRA adapters (ops.lora): a step whose metadata carries ``row_slot`` adds the rows'
+        # deltas to QKV, O and down from the metadata's table, else from this one (None: no table)
+        self.lora: Optional["ops.LoRATable"] = None
         self.cos_sin = ops.rope_cos_sin(self.D, cfg.max_position, cfg.rope_theta, cfg.rope_scaling,
                                         device=self.device)
 
@@ -215,8 +218,17 @@ class DecoderModel:
         x = ops.embedding(ids, self.w["embed"], self.vocab_start, self.vocab_end)
         return comm.tp_all_reduce(x) if self.tp_size > 1 else x
 
+    def _lora_delta(self, out, x: torch.Tensor, i: int, group: str, row_slot: torch.Tensor, table=None):
+        """``out`` (what ``linear`` returned for ``x``: a tensor or split-K ``Slabs``) plus the rows'
+        adapter deltas, before its consumer reads it."""
+        table = table if table is not None else self.lora
+        if table is None:
+            raise RuntimeError("a step with adapter rows and no LoRA table")
+        return ops.lora_delta(x, out, table, i, group, row_slot)
+
     def mlp(self, i: int, h: torch.Tensor, reduce: bool = True,
-            fuse_residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+            fuse_residual: Optional[torch.Tensor] = None, row_slot: Optional[torch.Tensor] = None,
+            lora=None) -> torch.Tensor:
         p = f"layers.{i}."
         w = self.w[p + "gate_up"]
         if w is None:                             # kept only fragment-tiled (ops.gemm.TILED_ONLY)
@@ -226,8 +238,11 @@ class DecoderModel:
             a = linear(h, w, epilogue="silu", wt=self.wt.get(p + "gate_up"))  # fused SiLU(gate)*up
         # TP=1: decode-size batches return split-K slabs, reduced by the next add+RMSNorm; prefill
         # sizes may add the residual stream in the GEMM epilogue (fuse_residual -> ResidualSum)
+        # a step with adapter rows keeps the residual add out of the GEMM: the delta comes first
         out = linear(a, self.w[p + "down"], wt=self.wt.get(p + "down"), slabs=self.tp_size == 1,
-                     fuse_residual=fuse_residual)
+                     fuse_residual=fuse_residual if row_slot is None else None)
+        if row_slot is not None:
+            out = self._lora_delta(out, a, i, "down", row_slot, lora)
         return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out
 
     def attention(self, i: int, h: torch.Tensor, positions: torch.Tensor, meta: AttentionMetadata,
@@ -237,7 +252,8 @@ class DecoderModel:
         kc, vc = kv.k(i), kv.v(i)
         scale, qpre = self.scale, False
         kvs = kv.scales(i)                        # fp8 cache: this layer's per-head scales (else None)
-        if qkv_rope_fused(h, self.w[p + "qkv"], self.D, kc):
+        rs = meta.row_slot                        # [T] adapter slot per row (None: no row has one)
+        if rs is None and qkv_rope_fused(h, self.w[p + "qkv"], self.D, kc):
             # prefill step: QKV GEMM with RoPE + paged KV write in its epilogue (K3+K4+K5, one pass).
             # PRESCALE_Q: q leaves it times scale * log2(e) at its one bf16 rounding, so the prefill
             # attention's block loop needs no per-score multiply (the prescaled-Q fold) without the
@@ -252,6 +268,8 @@ class DecoderModel:
             # QKV is column-parallel: even under TP its split-K slabs go straight to the RoPE/KV-write
             # pass (no all-reduce in between), unlike the row-parallel O / down projections
             qkv = linear(h, self.w[p + "qkv"], wt=self.wt.get(p + "qkv"), slabs=True)
+            if rs is not None:                    # the unfused path: the delta lands before RoPE / KV write
+                qkv = self._lora_delta(qkv, h, i, "qkv", rs, meta.lora)
             q = ops.rope_kv_write(qkv, positions, self.cos_sin, meta.slots, kc, vc, self.hq, self.hkv, self.D,
                                   kv_scales=kvs)
         attn = torch.empty_like(q)
@@ -280,8 +298,11 @@ class DecoderModel:
         elif meta.num_decode > 0:
             ops.decode(q[tp:], meta.ctx_lens_d, meta.block_tables_d, kc, vc, scale,
                        workspace=meta.decode_ws, out=attn[tp:], kv_scales=kvs)
-        out = linear(attn.view(T, self.hq * self.D), self.w[p + "o"], wt=self.wt.get(p + "o"),
-                     slabs=self.tp_size == 1, fuse_residual=fuse_residual)
+        attn = attn.view(T, self.hq * self.D)
+        out = linear(attn, self.w[p + "o"], wt=self.wt.get(p + "o"), slabs=self.tp_size == 1,
+                     fuse_residual=fuse_residual if rs is None else None)
+        if rs is not None:
+            out = self._lora_delta(out, attn, i, "o", rs, meta.lora)
         return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out
 
     def uses_sp(self, T: int) -> bool:
@@ -476,7 +497,8 @@ class DecoderModel:
             fr = residual if self.tp_size == 1 else None
             a = self.attention(i, h, positions, meta, kv, fuse_residual=fr)
             h = ops.rms_norm(a, self.w[p + "post_norm"], c.norm_eps, residual=residual)
-            x = self.mlp(i, h, fuse_residual=fr)
+            x = self.mlp(i, h, fuse_residual=fr) if meta.row_slot is None else self.mlp(i, h, row_slot=meta.row_slot,
+                                                                                                lora=meta.lora)
         return ops.rms_norm(x, self.w["final_norm"], c.norm_eps, residual=residual)
 
     def lm_weight(self) -> torch.Tensor:

@@ -17,6 +17,8 @@ from .sampling import (apply_top_k_top_p, fused_lm_head_ok, fused_logprob_ok, lm
 from .constrain import FsmTables, build_masks, sample_constrained
 from . import penalty
 from .penalty import PenaltyTable, apply_penalties
+from . import lora
+from .lora import LoRATable, lora_delta
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
            "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",

@@ -33,7 +33,7 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
     llm = llm or StubLLM()
     if not serving.tools:
         agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
-                           respond_penalties=serving.respond_penalties())
+                           respond_penalties=serving.respond_penalties(), **serving.adapter_kwargs())
     else:
         agent = LLMAgent(llm, make_retrieval_tool(retrieval),
                          extra_tools=[make_plot_tool()], temperature=serving.temperature,
@@ -43,7 +43,7 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
                          decide_logprobs=serving.decide_logprobs,
                          decide_confidence_threshold=serving.decide_confidence_threshold,
                          decide_top_logprobs=serving.decide_top_logprobs,
-                         respond_penalties=serving.respond_penalties())
+                         respond_penalties=serving.respond_penalties(), **serving.adapter_kwargs())
     return Services(db=db, kafka=kafka, agent=agent, retrieval=retrieval, serving=serving)
 
 
@@ -60,6 +60,8 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
     serving = serving or config.ServingConfig.from_env()
     from ..retrieval.ingest import build_store
     engine = AsyncEngine(engine_cfg)
+    for name, path in (serving.lora_adapters or {}).items():      # PENNY_LORA_ADAPTERS: loaded at start
+        engine.load_adapter(name, path)
     embedder, store = build_store(retrieval_cfg.embed_model, retrieval_cfg.device, retrieval_cfg.corpus_path,
                                   weights=retrieval_cfg.weights, vocab=retrieval_cfg.vocab)
     if retrieval_cfg.corpus_size and not retrieval_cfg.corpus_path:
@@ -70,7 +72,7 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
                     constrain_tools=serving.constrain_toolcalls, fsm_max_states=engine_cfg.fsm_max_states)
     if not serving.tools:
         agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
-                           respond_penalties=serving.respond_penalties())
+                           respond_penalties=serving.respond_penalties(), **serving.adapter_kwargs())
     else:
         agent = LLMAgent(llm, make_retrieval_tool(retrieval), extra_tools=[make_plot_tool()],
                          temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
@@ -79,7 +81,7 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
                          decide_logprobs=serving.decide_logprobs,
                          decide_confidence_threshold=serving.decide_confidence_threshold,
                          decide_top_logprobs=serving.decide_top_logprobs,
-                         respond_penalties=serving.respond_penalties())
+                         respond_penalties=serving.respond_penalties(), **serving.adapter_kwargs())
     return Services(db=db or Database(), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)
 

@@ -54,6 +54,10 @@ def parse(argv=None):
     ap.add_argument("--constrain-toolcalls", action="store_true",
                     default=os.environ.get("PENNY_CONSTRAIN_TOOLCALLS", "0").lower() in ("1", "true", "yes"),
                     help="decide calls sample under the tool-call token automaton (TP = 1 only)")
+    ap.add_argument("--lora", action="append", default=None, metavar="NAME=DIR",
+                    help="load a LoRA adapter (PEFT directory) under NAME at start; repeatable (PENNY_LORA_ADAPTERS)")
+    ap.add_argument("--decide-adapter", default=None, help="adapter the decide call runs on (PENNY_DECIDE_ADAPTER)")
+    ap.add_argument("--respond-adapter", default=None, help="adapter the respond call runs on (PENNY_RESPOND_ADAPTER)")
     ap.add_argument("--respond-repetition-penalty", type=float, default=None,
                     help="repetition penalty of the streamed respond call (PENNY_RESPOND_REPETITION_PENALTY; 1: off)")
     ap.add_argument("--respond-presence-penalty", type=float, default=None,
@@ -92,13 +96,19 @@ def build_leader_services(args, engine, device):
     retrieval = RetrievalService(embedder, store)
     flags = {f"respond_{k}_penalty": getattr(args, f"respond_{k}_penalty", None)
              for k in ("repetition", "presence", "frequency")}
+    if getattr(args, "lora", None):
+        flags["lora_adapters"] = config.parse_lora_adapters(args.lora)
+    flags["decide_adapter"], flags["respond_adapter"] = (getattr(args, "decide_adapter", None),
+                                                         getattr(args, "respond_adapter", None))
     serving = config.ServingConfig.from_env(**{k: v for k, v in flags.items() if v is not None})
+    for name, path in (serving.lora_adapters or {}).items():      # --lora / PENNY_LORA_ADAPTERS: loaded at start
+        engine.load_adapter(name, path)
     llm = EngineLLM(engine, max_model_len=args.max_model_len, history_token_budget=serving.history_token_budget,
                     constrain_tools=args.constrain_toolcalls or serving.constrain_toolcalls,
                     fsm_max_states=config.EngineConfig.from_env().fsm_max_states)
     if args.no_tools or not serving.tools:
         agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
-                           respond_penalties=serving.respond_penalties())
+                           respond_penalties=serving.respond_penalties(), **serving.adapter_kwargs())
     else:
         from .factory import retrieval_limit_tokens
         agent = LLMAgent(llm, make_retrieval_tool(retrieval), extra_tools=[make_plot_tool()],
@@ -109,7 +119,7 @@ def build_leader_services(args, engine, device):
                          decide_confidence_threshold=serving.decide_confidence_threshold,
                          decide_top_logprobs=(serving.decide_top_logprobs if args.decide_top_logprobs is None
                                               else args.decide_top_logprobs),
-                         respond_penalties=serving.respond_penalties())
+                         respond_penalties=serving.respond_penalties(), **serving.adapter_kwargs())
     broker = InMemoryBroker() if args.smoke else None
     return Services(db=Database(uri="" if args.smoke else None), kafka=KafkaClient(broker=broker), agent=agent,
                     engine=engine, retrieval=retrieval, serving=serving)
