@@ -1029,6 +1029,128 @@ def bench_lora(dev, Ms=(16, 64, 128, 256, 2048, 8192), ranks=(16, 64)) -> List[D
     return out
 
 
+def bench_kv_tier(dev, ns=(1, 16, 72), ttft_rounds: int = 3) -> List[Dict]:
+    """Host-memory KV tier (ops.kv_tier, engine.kv_host_tier) at the Llama-3-8B and -70B block shapes
+    (L = 32 / 80, Hkv = 8, D = 128), bf16 and fp8.  (a) gather and scatter of n blocks, interleaved: payload
+    GB/s (bytes of the blocks once; the kernels read and write them, so HBM traffic is twice that), ids
+    rotated between calls so that a small n is not served from the caches; (b) D2H and H2D of a 16-block
+    staging chunk through pinned memory; (c) on a Llama-3-8B engine (random weights), time to first token
+    of a 4608-token prompt with an 8-token reply, three engines sharing one model, interleaved per round:
+    the prefix resident in HBM, restored from the tier after filler prompts evicted it, and recomputed
+    after the same fillers with the tier off (the path without this feature).  Median with min and max."""
+    out = []
+    for model, L in (("8b", 32), ("70b", 80)):
+        for kvd, elt in (("bf16", 2), ("fp8", 1)):
+            planes, pb, nb = 2 * L, 8 * KV_BS * 128 * elt, 192
+            pool = torch.empty((planes, nb, pb), dtype=torch.uint8, device=dev).random_(0, 256)
+            staging = torch.empty((max(ns), planes, pb), dtype=torch.uint8, device=dev).random_(0, 256)
+            bpb = planes * pb
+            for n in ns:
+                g = torch.Generator().manual_seed(n)
+                idsets = [torch.randperm(nb, generator=g)[:n].to(torch.int32).to(dev) for _ in range(8)]
+                turn = {"gather": 0, "scatter": 0}
+
+                def mk(which, op):
+                    def f():
+                        turn[which] = (turn[which] + 1) % len(idsets)
+                        op(pool, idsets[turn[which]], staging)
+                    return f
+                fns = {"gather": mk("gather", ops.gather_blocks), "scatter": mk("scatter", ops.scatter_blocks)}
+                for f in fns.values():
+                    f()
+                torch.cuda.synchronize()
+                res = {k: [] for k in fns}
+                for _ in range(7):
+                    for k, f in fns.items():
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        for _ in range(10):
+                            f()
+                        b.record()
+                        b.synchronize()
+                        res[k].append(a.elapsed_time(b) * 1e3 / 10)
+                row = {"bench": "kv_tier_kernels", "model": model, "kv_dtype": kvd, "n_blocks": n,
+                       "block_mib": round(bpb / 2 ** 20, 2)}
+                for k, v in res.items():
+                    med = statistics.median(v)
+                    row.update({f"{k}_us": round(med, 1), f"{k}_us_min": round(min(v), 1), f"{k}_us_max": round(max(v), 1),
+                                f"{k}_payload_gbs": round(n * bpb / med / 1e3, 1)})
+                out.append(row)
+            # (b) one 16-block chunk over PCIe, each direction
+            chunk = staging[:16]
+            host = torch.empty(chunk.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(chunk)
+            r = interleaved({"d2h": lambda: host.copy_(chunk, non_blocking=True),
+                             "h2d": lambda: chunk.copy_(host, non_blocking=True)}, rounds=7, iters=4)
+            out.append({"bench": "kv_tier_pcie", "model": model, "kv_dtype": kvd, "chunk_blocks": 16,
+                        "chunk_mib": round(16 * bpb / 2 ** 20, 1),
+                        **{f"{k}_us": round(v, 1) for k, v in r.items()},
+                        **{f"{k}_gbs": round(16 * bpb / v / 1e3, 1) for k, v in r.items()}})
+            del pool, staging, host, chunk
+            torch.cuda.empty_cache()
+    out += _bench_kv_tier_ttft(dev, ttft_rounds)
+    return out
+
+
+def _bench_kv_tier_ttft(dev, rounds: int, prompt_tokens: int = 4608, model_name: str = "llama3-8b") -> List[Dict]:
+    import time
+
+    from ..config import EngineConfig
+    from ..engine import LLMEngine, SamplingParams
+    from ..models import build_model
+    base = dict(model=model_name, device="cuda", max_model_len=8192, max_num_seqs=4, graph_batch_sizes=(1, 2),
+                host_kv_gb=0.0)
+    model = build_model(EngineConfig(**base), dev)
+    full = (prompt_tokens - 1) // KV_BS
+    engines = {"resident": LLMEngine(EngineConfig(num_kv_blocks=512, **base), model=model)}
+    tok = engines["resident"].tokenizer
+    engines["restored"] = LLMEngine(EngineConfig(num_kv_blocks=160, **{**base, "host_kv_gb": 4.0},
+                                                 host_kv_chunk_blocks=40), model=model, tokenizer=tok)
+    engines["recomputed"] = LLMEngine(EngineConfig(num_kv_blocks=160, **base), model=model, tokenizer=tok)
+    V = model.cfg.vocab_size
+    prompt = [(1000 + i * 7919) % (V - 10) for i in range(prompt_tokens)]
+    sp = SamplingParams(temperature=0.0, max_tokens=8, ignore_eos=True)
+
+    def run(eng, ids):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        seq = eng.add_request(f"r{time.perf_counter_ns()}", ids, sp)
+        while seq.first_token_time is None:
+            eng.step()
+        ttft = seq.first_token_time - t0
+        while eng.has_work():
+            eng.step()
+        return 1e3 * ttft, seq
+
+    def fillers(eng, r):
+        for k in range(3):
+            run(eng, [(50_000 + 10_007 * (3 * r + k) + i * 104_729) % (V - 10) for i in range(prompt_tokens + 100)])
+
+    for eng in engines.values():                       # first run: graphs captured, the prompt's KV computed
+        run(eng, prompt)
+    ttft = {k: [] for k in engines}
+    cached = {k: [] for k in engines}
+    for r in range(rounds):
+        for name, eng in engines.items():
+            if name != "resident":
+                fillers(eng, r)
+            if eng.tier is not None:
+                eng.tier.synchronize()
+            ms, seq = run(eng, prompt)
+            ttft[name].append(ms)
+            cached[name].append(seq.num_cached_prompt // KV_BS)
+    st = engines["restored"].stats()
+    rows = []
+    for name in engines:
+        v = ttft[name]
+        rows.append({"bench": "kv_tier_ttft", "model": model_name, "prompt_tokens": prompt_tokens, "prefix_blocks": full,
+                     "variant": name, "ttft_ms": round(statistics.median(v), 2), "ttft_ms_min": round(min(v), 2),
+                     "ttft_ms_max": round(max(v), 2), "rounds": rounds, "cached_blocks": cached[name]})
+    rows.append({"bench": "kv_tier_ttft_stats", **{k: v for k, v in st.items() if k.startswith("host_kv")},
+                 "kv_evictions": st["kv_evictions"]})
+    return rows
+
+
 def bench_bge_query(dev) -> List[Dict]:
     """bge-base encoder latency on retrieval-size query batches (the per-turn critical path): the
     four projections on hipBLASLt (+ the GELU pass) vs the tile kernel with the bias / bias+GELU
@@ -2077,6 +2199,7 @@ def main(argv=None) -> int:
                 "lm_head_sample_logprob": bench_lm_head_sample_logprob,
                 "topn_logprob": bench_topn_logprob,
                 "lora": bench_lora,
+                "kv_tier": bench_kv_tier,
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),

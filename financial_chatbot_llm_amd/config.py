@@ -181,6 +181,33 @@ class EngineConfig:
     # allocated at the first load_adapter: at Llama-3-8B with the default rank about 92 MB per slot
     max_loras: int = 4
     lora_max_rank: int = 16
+    # host-memory KV tier (engine.kv_host_tier): GB (2^30 bytes) of pinned host DRAM that keep full KV blocks after
+    # HBM recycles them; a later prompt that matches them gets the bytes back over PCIe instead of a
+    # prefill, and a preempted sequence is swapped instead of recomputed.  0: off (the default, read from
+    # PENNY_HOST_KV_GB when the config is constructed).  TP = CP = 1 with prefix caching only.
+    host_kv_gb: float = field(default_factory=lambda: float(os.getenv("PENNY_HOST_KV_GB", "0") or 0))
+    host_kv_chunk_blocks: int = 16          # blocks per device staging chunk (two chunks per direction)
+
+    def __post_init__(self):
+        self.check_host_kv()
+
+    def check_host_kv(self) -> None:
+        """ValueError naming the cause when the host KV tier is on in a form it does not support."""
+        gb = float(self.host_kv_gb or 0)
+        if gb < 0:
+            raise ValueError(f"host_kv_gb must be >= 0, got {gb}")
+        if gb == 0:
+            return
+        if self.tp_size > 1 or self.shard_of_tp:
+            raise ValueError("host_kv_gb: the host KV tier does not support tensor parallel engines (tp_size > 1): "
+                             "every rank would need its own store and the same restore decisions")
+        if self.cp_size > 1:
+            raise ValueError("host_kv_gb: the host KV tier does not support context parallel engines (cp_size > 1)")
+        if not self.enable_prefix_caching:
+            raise ValueError("host_kv_gb: the host KV tier needs enable_prefix_caching=True (restored blocks "
+                             "enter the prefix cache)")
+        if int(self.host_kv_chunk_blocks) < 1:
+            raise ValueError(f"host_kv_chunk_blocks must be >= 1, got {self.host_kv_chunk_blocks}")
 
     @classmethod
     def from_env(cls, **overrides) -> "EngineConfig":

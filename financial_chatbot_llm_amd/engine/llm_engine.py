@@ -30,6 +30,7 @@ from ..utils.logging import get_logger
 from ..utils.metrics import METRICS
 from ..utils.profiling import StepProfiler, marker
 from .block_manager import make_block_manager
+from .kv_host_tier import STAT_KEYS as HOST_KV_STAT_KEYS, HostKVTier, TieredBlockManager
 from .model_runner import (CollectiveTimeout, ModelRunner, StepInputs, build_step_inputs, penalised,
                            prefill_step_inputs, sample_rows)
 from .scheduler import Scheduler, StepCostModel
@@ -132,6 +133,14 @@ class LLMEngine:
                           dtype=getattr(self.model, "dtype", torch.bfloat16), device=device, kv_dtype=kv_dtype,
                           k_scale=ks, v_scale=vs)
         self.bm = make_block_manager(nblocks, KV_BS, cfg.enable_prefix_caching)
+        # host-memory KV tier (kv_host_tier): off -> self.bm is the plain manager and nothing is allocated
+        self.tier = None
+        if float(getattr(cfg, "host_kv_gb", 0) or 0) > 0:
+            cfg.check_host_kv()
+            if getattr(self.model, "tp_size", 1) > 1:
+                raise ValueError("host_kv_gb: the host KV tier does not support tensor parallel engines")
+            self.tier = HostKVTier(self.kv, int(float(cfg.host_kv_gb) * 2 ** 30 + 0.5), int(cfg.host_kv_chunk_blocks))
+            self.bm = TieredBlockManager(self.bm, self.tier)
         base, per_row, per_tok = cfg.step_cost_ms
         self.scheduler = Scheduler(self.bm, cfg.max_num_seqs, cfg.max_num_batched_tokens, cfg.max_model_len,
                                    token_quantum=cfg.step_token_quantum if device.type == "cuda" else 0,
@@ -256,6 +265,7 @@ class LLMEngine:
                 self._pen_queue.remove(seq)
                 seq.status = SeqStatus.FINISHED
             else:
+                seq.kv_discard = True           # the host KV tier saves nothing of an aborted request
                 self.scheduler.abort(seq)
             seq.finish_reason = "abort"
             self._pen_release(seq)
@@ -404,6 +414,7 @@ class LLMEngine:
         self._inflight = None
         for seq in list(self.requests.values()):
             if not seq.finished:
+                seq.kv_discard = True           # stale hidden states: nothing of it enters the host KV tier
                 self.scheduler.abort(seq)
                 seq.finish_reason = "error"
         self.requests.clear()
@@ -777,6 +788,8 @@ class LLMEngine:
                 comm.broadcast_step(si)
                 self.timing["c4_s"] = self.timing.get("c4_s", 0.0) + time.perf_counter() - tb
             t1 = time.perf_counter()
+            if self.tier is not None:
+                self.tier.drain()              # queued saves, then restores, in front of this step
             launched = (batch, self._samplers(batch), self.runner.launch(si))
             # teacher-forced drafts were verified at _advance: drop the rejected tail now that the
             # chunk (all of it, as a real verification computes) is on its way
@@ -812,6 +825,8 @@ class LLMEngine:
         if self.ps.tp_size > 1:
             comm.broadcast_step(si)
         t1 = time.perf_counter()
+        if self.tier is not None:
+            self.tier.drain()                  # queued saves, then restores, in front of this step
         pending = self.runner.launch(si)
         sampled = pending.result()
         logprobs = self._row_values(pending)
@@ -956,6 +971,8 @@ class LLMEngine:
         seq = Sequence(f"score-{id(ids)}", ids[:rows], SamplingParams(temperature=0.0, max_tokens=1))
         if ad is not None:
             seq.lora_slot, seq.cache_salt = ad["slot"], ad["salt"]
+        if self.tier is not None:
+            self.tier.drain()       # queued saves read their blocks before this call may borrow them
         if not self.bm.grow(seq, rows):
             raise RuntimeError(f"score(): {self.bm.blocks_needed(seq, rows)} KV blocks needed, "
                                f"{self.bm.num_free()} free")
@@ -990,6 +1007,8 @@ class LLMEngine:
                 "kv_dtype": self.kv.kv_dtype,
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),
+                # host-memory KV tier (kv_host_tier): zeros while it is off
+                **(self.tier.stats() if self.tier is not None else dict.fromkeys(HOST_KV_STAT_KEYS, 0)),
                 "preemptions": self.scheduler.num_preemptions,
                 "time_capped_steps": self.scheduler.num_capped_steps,
                 "burst_steps": self.scheduler.num_burst_steps,

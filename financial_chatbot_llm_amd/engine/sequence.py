@@ -146,6 +146,12 @@ class Sequence:
         # base model; an adapter's salt, so its KV is shared with requests on the same load of it only)
         self.lora_slot = -1
         self.cache_salt = 0
+        # host-memory KV tier (kv_host_tier): kv_discard -- nothing of the sequence is saved when its
+        # blocks are freed (an abort); tier_wait -- a preempted sequence's admission is put off until
+        # the pool can take it back whole from the tier, tier_waits -- how often that has happened
+        self.kv_discard = False
+        self.tier_wait = False
+        self.tier_waits = 0
 
     def fsm_state_before(self, k: int) -> int:
         """Local automaton state in front of output token k (every earlier token known; -1: the

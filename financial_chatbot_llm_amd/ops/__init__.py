@@ -19,6 +19,8 @@ from . import penalty
 from .penalty import PenaltyTable, apply_penalties
 from . import lora
 from .lora import LoRATable, lora_delta
+from . import kv_tier
+from .kv_tier import gather_blocks, scatter_blocks
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
            "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",

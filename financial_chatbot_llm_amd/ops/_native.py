@@ -83,6 +83,8 @@ _SIGS = {
     "penny_pen_apply": [P, c_int, c_long, P, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P],
     "penny_lora_shrink": [P, c_long, P, P, c_int, c_int, c_int, P, c_int, c_int, P],
     "penny_lora_expand": [P, c_int, P, P, P, P, c_int, P, c_int, c_int, P, c_int, c_long, c_int, c_int, P],
+    "penny_kv_gather_blocks": [P, c_long, c_long, c_int, c_int, P, c_int, P, P],
+    "penny_kv_scatter_blocks": [P, c_long, c_long, c_int, c_int, P, c_int, P, P],
     "penny_lm_head_sample": [P, c_int, P, c_int, c_int, c_int, P, P, P, P, P],
     "penny_lm_head_sample_shard": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],
     "penny_lm_head_logprob": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],

@@ -69,6 +69,9 @@ def parse(argv=None):
                     help="KV pool element type (fp8: e4m3, twice the tokens in the same memory; TP = CP = 1)")
     ap.add_argument("--kv-scales", default=os.environ.get("PENNY_KV_SCALES") or None,
                     help="fp8 KV scales file (safetensors: k_scale, v_scale [layers, kv heads])")
+    ap.add_argument("--host-kv-gb", type=float, default=None,
+                    help="GB of pinned host memory behind the KV pool: evicted prefix blocks are restored over "
+                         "PCIe instead of recomputed (PENNY_HOST_KV_GB; 0: off; TP = CP = 1)")
     ap.add_argument("--device", default=None)
     ap.add_argument("--no-http", action="store_true")
     ap.add_argument("--smoke", action="store_true", help="serve one synthetic turn from the in-memory broker and exit")
@@ -161,6 +164,7 @@ def main(argv=None) -> int:
     ecfg = config.EngineConfig.from_env(model=args.model, tp_size=args.tp, max_model_len=args.max_model_len,
                                         device=dev_type, use_cuda_graph=dev_type == "cuda", cp_size=args.cp,
                                         kv_dtype=args.kv_dtype, kv_scales=args.kv_scales,
+                                        **({"host_kv_gb": args.host_kv_gb} if args.host_kv_gb is not None else {}),
                                         # a CP follower never decodes: a token KV pool, no graphs
                                         **({"num_kv_blocks": 16} if cp_follower else {}))
     engine = LLMEngine(ecfg)
