@@ -581,6 +581,53 @@ def bench_topk(dev) -> List[Dict]:
     return out
 
 
+def bench_hybrid_topk(dev, runs: int = 2) -> List[Dict]:
+    """Hybrid (dense + BM25) filtered top-k against ``filtered_topk`` at the shapes of ``bench_topk``, the three
+    variants interleaved in one process: dense, hybrid at alpha = 0.5 and hybrid at alpha = 1 (which reads no
+    vector bytes).  The term table is synthetic: four field labels every row carries, a merchant out of 24, a
+    category out of 10 and 0..10 rare terms (6..16 of the 32 slots); queries name a merchant, a category and a
+    label.  The whole measurement is repeated ``runs`` times to show the spread.  Also: ``lex_df_add`` over the
+    1M rows (the field labels put 4M of its adds on four buckets)."""
+    from ..ops.retrieval import DF_BUCKETS, DOC_TERMS, QUERY_TERMS
+    N, D = 1_000_000, 768
+    g = torch.Generator(device=dev).manual_seed(0)
+    corpus = torch.nn.functional.normalize(torch.randn((N, D), device=dev, generator=g), dim=-1).to(torch.bfloat16)
+    users = torch.randint(0, 10_000, (N,), device=dev, dtype=torch.int32, generator=g)
+    dates = torch.randint(0, 1 << 30, (N,), device=dev, dtype=torch.int64, generator=g)
+    terms = torch.zeros((N, DOC_TERMS), device=dev, dtype=torch.int32)
+    terms[:, :4] = torch.tensor([11, 12, 13, 14], device=dev, dtype=torch.int32)
+    terms[:, 4] = 1000 + torch.randint(0, 24, (N,), device=dev, generator=g).to(torch.int32)
+    terms[:, 5] = 2000 + torch.randint(0, 10, (N,), device=dev, generator=g).to(torch.int32)
+    rare = torch.randint(1 << 16, 1 << 31, (N, 10), device=dev, generator=g).to(torch.int32)
+    keep = torch.arange(10, device=dev)[None, :] < torch.randint(0, 11, (N, 1), device=dev, generator=g)
+    terms[:, 6:16] = rare * keep
+    df = torch.zeros((DF_BUCKETS,), device=dev, dtype=torch.int32)
+    ops.lex_df_add(terms, df)
+    total = int((terms != 0).sum())
+    out = [{"op": "lex_df_add", "N": N, "us": round(timeit(lambda: ops.lex_df_add(terms, df), iters=5), 1)}]
+    for run in range(runs):
+        for nq in (1, 32, 64):
+            q = torch.nn.functional.normalize(torch.randn((nq, D), device=dev, generator=g), dim=-1).to(torch.bfloat16)
+            qu = torch.randint(0, 10_000, (nq,), device=dev, dtype=torch.int32, generator=g)
+            qf = torch.zeros((nq,), device=dev, dtype=torch.int64)
+            ks = torch.full((nq,), 20, device=dev, dtype=torch.int32)
+            qt = torch.zeros((nq, QUERY_TERMS), device=dev, dtype=torch.int32)
+            qt[:, 0] = 1000 + torch.randint(0, 24, (nq,), device=dev, generator=g).to(torch.int32)
+            qt[:, 1] = 2000 + torch.randint(0, 10, (nq,), device=dev, generator=g).to(torch.int32)
+            qt[:, 2] = 12
+            w = {a: ops.hybrid_query_weights(qt, a, df, N, total) for a in (0.5, 1.0)}
+
+            def hybrid(a):
+                u, dw, r = w[a]
+                return lambda: ops.filtered_topk_hybrid(corpus, users, dates, terms, q, qu, qf, ks, 20, qt, u, dw, r)
+            res = interleaved({"dense": lambda: ops.filtered_topk(corpus, users, dates, q, qu, qf, ks, 20),
+                               "hybrid_a0.5": hybrid(0.5), "hybrid_a1": hybrid(1.0)}, rounds=7, iters=10)
+            out.append({"op": "hybrid_topk", "run": run, "N": N, "nq": nq, **{f"{k}_us": round(v, 1) for k, v in res.items()},
+                        "ratio_a0.5": round(res["hybrid_a0.5"] / res["dense"], 3),
+                        "ratio_a1": round(res["hybrid_a1"] / res["dense"], 3)})
+    return out
+
+
 def bench_gemm(dev) -> List[Dict]:
     """hipBLASLt (torch.nn.functional.linear) on the Llama-3-8B projection shapes."""
     out = []
@@ -2173,7 +2220,7 @@ def main(argv=None) -> int:
     for name in args.only.split(","):
         res += {"decode": bench_decode, "decode_mixed": bench_decode_mixed, "decode_lean": bench_decode_lean, "kv_fp8_decode": bench_kv_fp8_decode,
                 "kv_fp8_prefill": bench_kv_fp8_prefill, "prefill": bench_prefill, "prefill_mixed": bench_prefill_mixed, "prefill_spec_split": bench_prefill_spec_split, "elementwise": bench_elementwise,
-                "topk": bench_topk, "gemm": bench_gemm, "gemm_prefill": bench_gemm_prefill, "lm_head": bench_lm_head, "lm_head_fused": bench_lm_head_fused, "lm_head_logprob": bench_lm_head_logprob, "bge_query": bench_bge_query, "gemm_tail": bench_gemm_tail,
+                "topk": bench_topk, "hybrid_topk": bench_hybrid_topk, "gemm": bench_gemm, "gemm_prefill": bench_gemm_prefill, "lm_head": bench_lm_head, "lm_head_fused": bench_lm_head_fused, "lm_head_logprob": bench_lm_head_logprob, "bge_query": bench_bge_query, "gemm_tail": bench_gemm_tail,
                 "gemm_tune": bench_gemm_tune_sweep, "skinny": bench_skinny, "splitk": bench_splitk,
                 "splitk_qkv": lambda d: bench_splitk(d, ("qkv",)), "gateup": bench_gateup, "moe": bench_moe,
                 "moe_prefill": bench_moe_prefill, "gemm_hip": bench_gemm_hip, "gemm_hip_quick": lambda d: bench_gemm_hip(d, [512, 1024, 2048, 3072, 4096]), "gemm_hip_check": check_gemm_hip, "gemm_lds_probe": gemm_lds_probe, "prefill_policy": bench_prefill_policy, "prefill_policy_quick": lambda d: bench_prefill_policy(d, [512, 1024, 1536, 2048, 2560, 3072, 3584, 4096]), "prefill_policy_70b": lambda d: bench_prefill_policy(d, [384, 512, 768, 1024, 1536, 2048, 2560, 3072, 4096], model="70b"),

@@ -261,6 +261,11 @@ class RetrievalConfig:
     vocab: Optional[str] = None             # BERT vocab.txt / tokenizer.json (None: hashed word ids)
     corpus_path: Optional[str] = None       # JSONL/Parquet transactions or a store snapshot to load
     device: str = "cuda"
+    hybrid_alpha: float = 0.0               # weight of the BM25 term score in the ranking (0: dense only)
+
+    def __post_init__(self):
+        if not 0.0 <= float(self.hybrid_alpha) <= 1.0:
+            raise ValueError(f"hybrid_alpha (PENNY_HYBRID_ALPHA) must lie in [0, 1], got {self.hybrid_alpha}")
 
     @classmethod
     def from_env(cls, **overrides) -> "RetrievalConfig":
@@ -273,6 +278,7 @@ class RetrievalConfig:
             vocab=os.getenv("PENNY_EMBED_VOCAB") or None,
             corpus_path=os.getenv("PENNY_CORPUS_PATH") or None,
             device=_env("PENNY_DEVICE", cls.device),
+            hybrid_alpha=_env_float("PENNY_HYBRID_ALPHA", cls.hybrid_alpha),
         )
         return dataclasses.replace(c, **overrides)
 

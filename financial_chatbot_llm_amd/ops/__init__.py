@@ -9,7 +9,8 @@ from .attention import (KV_BS, DecodeWorkspace, KVScales, decode, default_scale,
                         make_kv_scales, prefill, rope_cos_sin, rope_kv_write, write_kv_ref)
 from .embedding import embedding
 from .norm import layer_norm, rms_norm
-from .retrieval import filtered_topk
+from .retrieval import (filtered_topk, filtered_topk_hybrid, filtered_topk_hybrid_ref, hybrid_query_weights,
+                        lex_df_add)
 from .sampling import (apply_top_k_top_p, fused_lm_head_ok, fused_logprob_ok, lm_head_logprobs, lm_head_sample,
                        lm_head_sample_logprob, lm_head_sample_shard, lm_head_stream_sample,
                        lm_head_stream_sample_logprob, merge_logprob_stats, pick_pairs, sample, sample_shard,
@@ -24,4 +25,5 @@ from .kv_tier import gather_blocks, scatter_blocks
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
            "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",
+           "filtered_topk_hybrid", "filtered_topk_hybrid_ref", "hybrid_query_weights", "lex_df_add",
            "apply_top_k_top_p", "sample"]

@@ -104,6 +104,9 @@ _SIGS = {
     "penny_moe_combine": [P, P, c_int, c_int, c_int, P, P],
     "penny_moe_combine_weighted": [P, P, P, c_int, c_int, c_int, P, P],
     "penny_filtered_topk": [P, P, P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, P, c_int, P, P, P, P],
+    "penny_filtered_topk_hybrid": [P, P, P, c_long, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int,
+                                   P, P, P, P],
+    "penny_lex_df_add": [P, c_long, P, P],
 }
 
 

@@ -94,13 +94,18 @@ def iter_documents(path: str, batch_rows: int = 65536) -> Iterator[Dict[str, Any
 class CorpusIngestor:
     """Bulk-embed documents on the GPU and append them to a vector store."""
 
-    def __init__(self, embedder, store, batch_size: int = 1024, max_len: int = 128, lock=None):
-        """``lock`` (optional) is held around each batch's embed + append only, so a caller
+    def __init__(self, embedder, store, batch_size: int = 1024, max_len: int = 128, lock=None,
+                 lexical: bool = False):
+        """``lexical`` turns the store's term tables on (hybrid retrieval), building them for rows it
+        already holds; the store then extracts the terms of every batch it is given.
+        ``lock`` (optional) is held around each batch's embed + append only, so a caller
         that serialises searches on the same store with it (the serving RetrievalService) can
         interleave its searches between batches instead of waiting for the whole ingest."""
         self.embedder, self.store = embedder, store
         self.batch_size, self.max_len = batch_size, max_len
         self.lock = lock
+        if lexical:
+            ensure_lexical(store)
         self.docs = 0
         self.rejected = 0
         self.seconds = 0.0
@@ -153,9 +158,28 @@ class CorpusIngestor:
             torch.cuda.synchronize(dev)
 
 
+def ensure_lexical(store) -> bool:
+    """Make ``store`` serve hybrid queries: build the term tables it lacks from the rows' payload
+    texts.  Rows without payloads (a snapshot of vectors alone) cannot be rebuilt: one warning, and
+    the store keeps serving dense.  -> whether the store is lexical now."""
+    if getattr(store, "lexical", False):
+        return True
+    if not hasattr(store, "build_lexical"):
+        logger.warning("hybrid retrieval asked for, but this store keeps no term tables: serving dense")
+        return False
+    n = len(store.corpus)
+    if n and store.corpus.payload(0) is None and store.corpus.payload(n - 1) is None:
+        logger.warning("hybrid retrieval asked for, but the collection has no term tables and no payload texts "
+                       "to build them from: serving dense")
+        return False
+    store.build_lexical()
+    return True
+
+
 def build_store(embed_model: str, device: str, corpus_path: Optional[str], weights: Optional[str] = None,
-                vocab: Optional[str] = None) -> Tuple[Any, Any]:
-    """(embedder, store) for serving: load a snapshot directory, or ingest a document file."""
+                vocab: Optional[str] = None, lexical: bool = False) -> Tuple[Any, Any]:
+    """(embedder, store) for serving: load a snapshot directory, or ingest a document file.
+    ``lexical`` (hybrid_alpha > 0) gives the store term tables, built when a snapshot lacks them."""
     import os
 
     from .embedder import BgeEmbedder
@@ -164,8 +188,10 @@ def build_store(embed_model: str, device: str, corpus_path: Optional[str], weigh
     if corpus_path and os.path.isdir(corpus_path):
         store = DeviceVectorStore.load(corpus_path, device=device)
         logger.info(f"loaded collection snapshot {corpus_path}: {store.size} points")
+        if lexical:
+            ensure_lexical(store)
     else:
-        store = DeviceVectorStore(embedder.dim, device=device)
+        store = DeviceVectorStore(embedder.dim, device=device, lexical=lexical)
         if corpus_path:
             stats = CorpusIngestor(embedder, store).ingest(iter_documents(corpus_path))
             logger.info(f"ingested {corpus_path}: {stats}")
@@ -181,11 +207,12 @@ def main(argv=None) -> int:
     ap.add_argument("--vocab", default=None)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--lexical", action="store_true", help="also build the term tables of hybrid retrieval")
     a = ap.parse_args(argv)
     from .embedder import BgeEmbedder
     from .store import DeviceVectorStore
     emb = BgeEmbedder(a.embed_model, device=a.device, weights=a.weights, vocab=a.vocab)
-    store = DeviceVectorStore(emb.dim, device=a.device)
+    store = DeviceVectorStore(emb.dim, device=a.device, lexical=a.lexical)
     stats = CorpusIngestor(emb, store, batch_size=a.batch).ingest(iter_documents(a.input))
     if a.snapshot:
         store.save(a.snapshot)

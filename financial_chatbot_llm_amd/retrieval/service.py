@@ -20,8 +20,13 @@ logger = get_logger(__name__)
 
 
 class RetrievalService:
-    def __init__(self, embedder, store, max_batch: int = 64, window_s: float = 0.002):
+    def __init__(self, embedder, store, max_batch: int = 64, window_s: float = 0.002, hybrid_alpha: float = 0.0):
+        """``hybrid_alpha`` > 0 ranks by (1 - alpha) * cosine + alpha * normalised BM25 of the query
+        text's terms (stores built with ``lexical=True``); at 0 the store is called exactly as before."""
+        if not 0.0 <= float(hybrid_alpha) <= 1.0:
+            raise ValueError(f"hybrid_alpha {hybrid_alpha} outside [0, 1]")
         self.embedder, self.store = embedder, store
+        self.hybrid_alpha = float(hybrid_alpha)
         self.max_batch, self.window_s = max_batch, window_s
         self._pending: List[Tuple[str, str, Optional[int], int, asyncio.Future]] = []
         self._flush_task: Optional[asyncio.Task] = None
@@ -36,7 +41,12 @@ class RetrievalService:
             ctx = self._stream_ctx()
             with ctx:
                 q = self.embedder.embed(list(queries))
-                hits = self.store.search_batch(q, list(user_ids), list(date_gte), list(limits))
+                if self.hybrid_alpha > 0:
+                    hits = self.store.search_batch(q, list(user_ids), list(date_gte), list(limits),
+                                                   texts=list(queries), alpha=self.hybrid_alpha)
+                    METRICS.inc("retrieval_hybrid_queries_total", len(queries))
+                else:
+                    hits = self.store.search_batch(q, list(user_ids), list(date_gte), list(limits))
             METRICS.inc("retrieval_queries_total", len(queries))
             METRICS.inc("retrieval_batches_total")
             METRICS.set_gauge("retrieval_last_batch_s", now() - t0)

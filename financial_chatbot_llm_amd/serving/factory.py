@@ -28,8 +28,12 @@ def build_stub_services(broker: Optional[InMemoryBroker] = None, db: Optional[Da
     db = db or Database(uri="")
     kafka = KafkaClient(broker=broker or InMemoryBroker())
     embedder = embedder or HashEmbedder(768)
-    store = store or NumpyVectorStore(embedder.dim)
-    retrieval = RetrievalService(embedder, store)
+    alpha = config.RetrievalConfig.from_env().hybrid_alpha
+    store = store or NumpyVectorStore(embedder.dim, lexical=alpha > 0)
+    if alpha > 0:
+        from ..retrieval.ingest import ensure_lexical
+        ensure_lexical(store)
+    retrieval = RetrievalService(embedder, store, hybrid_alpha=alpha)
     llm = llm or StubLLM()
     if not serving.tools:
         agent = LLMService(llm, temperature=serving.temperature, max_response_tokens=serving.max_response_tokens,
@@ -63,10 +67,12 @@ def build_engine_services(engine_cfg: Optional[config.EngineConfig] = None,
     for name, path in (serving.lora_adapters or {}).items():      # PENNY_LORA_ADAPTERS: loaded at start
         engine.load_adapter(name, path)
     embedder, store = build_store(retrieval_cfg.embed_model, retrieval_cfg.device, retrieval_cfg.corpus_path,
-                                  weights=retrieval_cfg.weights, vocab=retrieval_cfg.vocab)
+                                  weights=retrieval_cfg.weights, vocab=retrieval_cfg.vocab,
+                                  lexical=retrieval_cfg.hybrid_alpha > 0)
     if retrieval_cfg.corpus_size and not retrieval_cfg.corpus_path:
-        store.load_synthetic(retrieval_cfg.corpus_size, retrieval_cfg.num_users)
-    retrieval = RetrievalService(embedder, store)
+        store.load_synthetic(retrieval_cfg.corpus_size, retrieval_cfg.num_users,
+                             lexical=retrieval_cfg.hybrid_alpha > 0)
+    retrieval = RetrievalService(embedder, store, hybrid_alpha=retrieval_cfg.hybrid_alpha)
     llm = EngineLLM(engine, max_model_len=engine_cfg.max_model_len,
                     history_token_budget=serving.history_token_budget,
                     constrain_tools=serving.constrain_toolcalls, fsm_max_states=engine_cfg.fsm_max_states)

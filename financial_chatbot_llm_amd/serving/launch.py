@@ -40,6 +40,9 @@ def parse(argv=None):
     ap.add_argument("--corpus-path", default=os.environ.get("PENNY_CORPUS_PATH", ""),
                     help="collection snapshot dir (DeviceVectorStore.save) or jsonl/json/parquet documents to ingest")
     ap.add_argument("--users", type=int, default=int(os.environ.get("PENNY_CORPUS_USERS", "10000")))
+    ap.add_argument("--hybrid-alpha", type=float, default=None, metavar="A",
+                    help="weight in [0, 1] of the BM25 term score in the retrieval ranking; 0 is dense only "
+                         "(default: PENNY_HYBRID_ALPHA, else 0)")
     ap.add_argument("--port", type=int, default=int(os.environ.get("PORT", "8000")))
     ap.add_argument("--tool-steps", type=int, default=1, help=">1 enables the multi-step agent (retrieval + plot)")
     ap.add_argument("--no-tools", action="store_true",
@@ -86,17 +89,20 @@ def build_leader_services(args, engine, device):
     from ..tools import make_plot_tool, make_retrieval_tool
     from .app import Services
 
+    overrides = {} if getattr(args, "hybrid_alpha", None) is None else {"hybrid_alpha": args.hybrid_alpha}
     if device.type == "cuda":
         from ..retrieval.ingest import build_store
-        rcfg = config.RetrievalConfig.from_env()
+        rcfg = config.RetrievalConfig.from_env(**overrides)
+        alpha = rcfg.hybrid_alpha
         embedder, store = build_store(args.embed_model, str(device), args.corpus_path or rcfg.corpus_path,
-                                      weights=rcfg.weights, vocab=rcfg.vocab)
+                                      weights=rcfg.weights, vocab=rcfg.vocab, lexical=alpha > 0)
         if args.corpus and not (args.corpus_path or rcfg.corpus_path):
-            store.load_synthetic(args.corpus, args.users)
+            store.load_synthetic(args.corpus, args.users, lexical=alpha > 0)
     else:
+        alpha = config.RetrievalConfig.from_env(**overrides).hybrid_alpha
         embedder = HashEmbedder(768)
-        store = NumpyVectorStore(768)
-    retrieval = RetrievalService(embedder, store)
+        store = NumpyVectorStore(768, lexical=alpha > 0)
+    retrieval = RetrievalService(embedder, store, hybrid_alpha=alpha)
     flags = {f"respond_{k}_penalty": getattr(args, f"respond_{k}_penalty", None)
              for k in ("repetition", "presence", "frequency")}
     if getattr(args, "lora", None):
