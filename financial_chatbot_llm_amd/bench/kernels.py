@@ -2204,6 +2204,155 @@ def bench_lm_head_stream(dev, V: int = 128256, K: int = 4096,
     return out
 
 
+DENSE_FP8_MODELS = {"8b": (4096, 14336, "llama3-8b"), "70b": (8192, 28672, None), "70b_tp8": (8192, 3584, None)}
+
+
+def _timeit_interleaved(fns: Dict[str, Callable[[], None]], iters: int, rounds: int = 7) -> Dict[str, float]:
+    """Median us per call of each variant, the variants taking turns inside every round (one process,
+    one clock state: what is compared is measured side by side)."""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    res = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            res[k].append(a.elapsed_time(b) * 1e3 / iters)
+    return {k: statistics.median(v) for k, v in res.items()}
+
+
+def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128, 256, 512, 2048),
+                        sweep: bool = False) -> List[Dict]:
+    """One dense Llama MLP (gate|up + SiLU, down; the fp8 path's two row-quantisation passes included):
+    fp8 weights (``ops.mlp_fp8``) against bf16 (``linear`` as ``DecoderModel.mlp`` calls it, tiled copies
+    and slabs as the model would hold them), interleaved in one process, the weights rotated over
+    copies so every call streams W from HBM.  Reports both times, which one wins, and for the fp8 path
+    each GEMM alone with the TB/s of its W bytes.  The 70B TP=8 row is one rank's shard: down returns
+    bf16 for the all-reduce.  ``sweep``: instead, every (S, ntf) candidate of the streaming kernel per
+    GEMM and M <= 256 (the numbers ``ops.fp8_dense.DENSE_FP8`` is chosen from)."""
+    from ..ops import _native as N
+    from ..ops import fp8_dense, gemm
+    out = []
+    g = torch.Generator(device=dev).manual_seed(0)
+    for model in models:
+        H, F_, tuning = DENSE_FP8_MODELS[model]
+        shard = model.endswith("tp8")
+        if tuning:
+            gemm.load_gemm_tuning(tuning)
+        copies = max(2, -(-(768 << 20) // (3 * H * F_)))
+        bcopies = max(2, -(-(768 << 20) // (6 * H * F_)))
+        q, bw = [], []
+        for c in range(max(copies, bcopies)):
+            gu = (torch.randn((2 * F_, H), device=dev, generator=g) * 0.02).to(torch.bfloat16)
+            dn = (torch.randn((H, F_), device=dev, generator=g) * 0.02).to(torch.bfloat16)
+            if c < copies:
+                q.append(fp8_dense.quantize_dense_mlp(gu, dn))
+            if c < bcopies and not sweep:
+                ent = {"gu": gu, "dn": dn, "gut": None, "dnt": None}
+                if gemm.uses_tiled_weight(2 * F_, H):
+                    ent["gut"] = gemm.tile_weight(gu)
+                    if gemm.tiled_only(2 * F_, H):
+                        ent["gu"] = None
+                if gemm.uses_tiled_weight(H, F_):
+                    ent["dnt"] = gemm.tile_weight(dn)
+                bw.append(ent)
+            del gu, dn
+        it = [0]
+
+        def nxt(n):
+            it[0] += 1
+            return it[0] % n
+
+        def bf16_mlp(h):
+            e = bw[nxt(bcopies)]
+            if e["gu"] is None:
+                a = gemm.linear_tiled(h, e["gut"], 2 * F_, epilogue="silu")
+            else:
+                a = gemm.linear(h, e["gu"], epilogue="silu", wt=e["gut"])
+            return gemm.linear(a, e["dn"], wt=e["dnt"], slabs=not shard)
+
+        for M in Ms:
+            h = torch.randn((M, H), device=dev, generator=g).to(torch.bfloat16)
+            if sweep:
+                if M > fp8_dense.MAX_M:
+                    continue
+                xq, xs = fp8_dense._quant(h)
+                a = torch.randn((M, F_), device=dev, generator=g).to(torch.bfloat16)
+                aq, as_ = fp8_dense._quant(a)
+                for name, (N_, K_), x_, s_, epi in (("gate_up", (2 * F_, H), xq, xs, "silu"),
+                                                    ("down", (H, F_), aq, as_, "bf16" if shard else "slabs")):
+                    fns = {}
+                    for ntf in (2, 4):
+                        for S in ((1, 2, 4, 7, 8, 14, 16) if epi == "slabs" else (1,)):
+                            if K_ % (128 * S) or N_ % (16 * ntf) or (N_ // (16 * ntf)) * S > 4096:
+                                continue
+                            wq = [(w.gate_up_q, w.gate_up_s) if name == "gate_up" else (w.down_q, w.down_s) for w in q]
+                            fns[f"S{S}_ntf{ntf}"] = (lambda S=S, ntf=ntf, wq=wq, x_=x_, s_=s_, epi=epi:
+                                                     fp8_dense.dense_fp8_gemm(x_, s_, *wq[nxt(copies)], epi, S, ntf))
+                    t = _timeit_interleaved(fns, iters=2 * copies, rounds=5)
+                    best = min(t, key=t.get)
+                    row = {"bench": "dense_fp8_sweep", "model": model, "M": M, name: {"shape": [N_, K_]}, "epi": epi,
+                           "us": {k: round(v, 1) for k, v in t.items()}, "best": best,
+                           "best_TBps": round(N_ * K_ / t[best] / 1e6, 2)}
+                    out.append(row)
+                    print(json.dumps(row), flush=True)
+                continue
+            w0 = q[0]
+            path = fp8_dense.mlp_fp8_path(h, w0)
+            fns = {"fp8": lambda: fp8_dense.mlp_fp8(h, q[nxt(copies)], slabs=not shard), "bf16": lambda: bf16_mlp(h)}
+            t = _timeit_interleaved(fns, iters=2 * max(copies, bcopies))
+            row = {"bench": "dense_fp8_mlp", "model": model, "M": M, "path": path, "fp8_us": round(t["fp8"], 1),
+                   "bf16_us": round(t["bf16"], 1), "speedup": round(t["bf16"] / t["fp8"], 2),
+                   "winner": "fp8" if t["fp8"] < t["bf16"] else "bf16"}
+            # the fp8 path's stages alone
+            xq, xs = fp8_dense._quant(h)
+            _, a = fp8_dense.mlp_fp8(h, w0)
+            aq, as_ = fp8_dense._quant(a)
+            st = N.stream
+            if path == "stream":
+                _, ntf1 = fp8_dense.dense_fp8_config(M, 2 * F_, H, "silu")
+                epi2 = "bf16" if shard else "slabs"
+                S2, ntf2 = fp8_dense.dense_fp8_config(M, H, F_, epi2)
+                parts = {"gate_up": lambda: fp8_dense.dense_fp8_gemm(xq, xs, q[nxt(copies)].gate_up_q, q[it[0] % copies].gate_up_s,
+                                                                     "silu", 1, ntf1),
+                         "down": lambda: fp8_dense.dense_fp8_gemm(aq, as_, q[nxt(copies)].down_q, q[it[0] % copies].down_s,
+                                                                  epi2, S2, ntf2)}
+                cfgs = {"gate_up": [1, ntf1], "down": [S2, ntf2]}
+            else:
+                off, ones = fp8_dense._bucket(dev, M)
+                ab = torch.empty((M, F_), dtype=torch.bfloat16, device=dev)
+                yb = torch.empty((M, H), dtype=torch.bfloat16, device=dev)
+
+                def g1():
+                    w = q[nxt(copies)]
+                    N.call("penny_moe_gemm_prefill_fp8", N.ptr(xq), H, None, N.ptr(xs), N.ptr(off), N.ptr(w.gate_up_q),
+                           N.ptr(w.gate_up_s), None, N.ptr(ab), F_, M, 1, 2 * F_, H, 7, st())
+
+                def g2():
+                    w = q[nxt(copies)]
+                    N.call("penny_moe_gemm_prefill_fp8", N.ptr(aq), F_, None, N.ptr(as_), N.ptr(off), N.ptr(w.down_q),
+                           N.ptr(w.down_s), N.ptr(ones), N.ptr(yb), H, M, 1, H, F_, 8, st())
+                parts = {"gate_up": g1, "down": g2}
+                cfgs = {"gate_up": "tile", "down": "tile"}
+            parts["quant_h"] = lambda: fp8_dense._quant(h)
+            parts["quant_a"] = lambda: fp8_dense._quant(a)
+            pt = _timeit_interleaved(parts, iters=2 * copies, rounds=5)
+            for name, (N_, K_) in (("gate_up", (2 * F_, H)), ("down", (H, F_))):
+                row[name] = {"shape": [N_, K_], "cfg": cfgs[name], "us": round(pt[name], 1),
+                             "W_TBps": round(N_ * K_ / pt[name] / 1e6, 2)}
+            row["quant_us"] = [round(pt["quant_h"], 1), round(pt["quant_a"], 1)]
+            out.append(row)
+            print(json.dumps(row), flush=True)
+        del q, bw
+        torch.cuda.empty_cache()
+    return out
+
+
 def interleave16_rows(w: torch.Tensor) -> torch.Tensor:
     from ..ops.gemm import interleave16
     half = w.shape[0] // 2
@@ -2247,6 +2396,8 @@ def main(argv=None) -> int:
                 "topn_logprob": bench_topn_logprob,
                 "lora": bench_lora,
                 "kv_tier": bench_kv_tier,
+                "dense_fp8_mlp": bench_dense_fp8_mlp,
+                "dense_fp8_sweep": lambda d: bench_dense_fp8_mlp(d, Ms=(1, 16, 64, 128, 256), sweep=True),
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),

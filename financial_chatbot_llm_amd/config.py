@@ -132,6 +132,11 @@ class EngineConfig:
     # fp8 scales: a safetensors file with k_scale, v_scale [num_layers, num_kv_heads] f32
     # (engine.kv_calibration.save_kv_scales); None -> 1
     kv_scales: Optional[str] = None
+    # dense Llama MLP weights (gate|up, down): "bf16" | "fp8" (OCP e4m3fn codes + one f32 scale per
+    # output row, dynamic per-row e4m3 activations: half the MLP's weight bytes resident and streamed
+    # per decode step; ops/fp8_dense.py).  Mixtral's experts take dtype="fp8" instead.  The default is
+    # read from PENNY_MLP_DTYPE when the config is constructed.
+    mlp_dtype: str = field(default_factory=lambda: os.getenv("PENNY_MLP_DTYPE", "bf16"))
     # of (free HBM after weights - 6 GiB); 0.92 leaves ~20 GiB of the 288 GiB unused at the end of
     # the 20/5 bench (engine stats hbm_used_gib: 8B 264.5, Mixtral fp8 267.9; 0.95 measured no
     # faster: profiles/r2_bench_kv_fraction.txt)
@@ -190,6 +195,8 @@ class EngineConfig:
 
     def __post_init__(self):
         self.check_host_kv()
+        if self.mlp_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"unknown mlp_dtype {self.mlp_dtype!r} (bf16 | fp8; PENNY_MLP_DTYPE)")
 
     def check_host_kv(self) -> None:
         """ValueError naming the cause when the host KV tier is on in a form it does not support."""

@@ -1004,7 +1004,7 @@ class LLMEngine:
                 "lora_steps": self.runner.stats["lora_steps"], "lora_rows": self.runner.stats["lora_rows"],
                 "lora_slots_used": len(self._adapters),
                 "lora_table_mb": round(self.runner.lora_table.num_bytes() / 1e6, 1) if self.runner.lora_table else 0.0,
-                "kv_dtype": self.kv.kv_dtype,
+                "kv_dtype": self.kv.kv_dtype, "mlp_dtype": getattr(self.model, "mlp_dtype", "bf16"),
                 "kv_usage": self.bm.usage(), "prefix_hit_rate": self.bm.hit_rate(),
                 "kv_blocks": self.bm.num_blocks, "kv_evictions": int(getattr(self.bm, "evictions", 0)),
                 # host-memory KV tier (kv_host_tier): zeros while it is off

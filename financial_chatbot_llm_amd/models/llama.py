@@ -38,7 +38,7 @@ def _dual_stream(device) -> "torch.cuda.Stream":
         _DUAL_STREAMS[key] = torch.cuda.Stream(device=device)
     return _DUAL_STREAMS[key]
 from ..ops.gemm import (interleave16, linear, linear_tiled, prefill_qkv_rope, qkv_rope_fused, tile_weight,
-                        tiled_only, uses_tiled_weight)
+                        tiled_only, untile_weight, uses_tiled_weight)
 from ..parallel.layers import shard_cols, shard_rows, shard_sections, vocab_range
 from .common import AttentionMetadata, KVCache, random_tensor
 from .configs import ModelConfig
@@ -84,6 +84,9 @@ class DecoderModel:
         # per-request LoRA adapters (ops.lora): a step whose metadata carries ``row_slot`` adds the rows'
         # deltas to QKV, O and down from the metadata's table, else from this one (None: no table)
         self.lora: Optional["ops.LoRATable"] = None
+        # dense MLP weights: "bf16", or "fp8" once quantize_mlp() replaced them by ops.DenseFp8MLP holders
+        self.mlp_dtype = "bf16"
+        self.mlp_q: Dict[int, "ops.DenseFp8MLP"] = {}
         self.cos_sin = ops.rope_cos_sin(self.D, cfg.max_position, cfg.rope_theta, cfg.rope_scaling,
                                         device=self.device)
 
@@ -206,6 +209,33 @@ class DecoderModel:
         self.w[name] = buf[:rows]
         self._lm_pad = buf
 
+    def quantize_mlp(self) -> "DecoderModel":
+        """bf16 gate|up and down of every layer -> fp8 e4m3 codes + f32 row scales (``ops.fp8_dense``),
+        quantised from this rank's shard; the bf16 weights and their fragment-tiled copies are dropped.
+        ``layers.i.gate_up_q`` / ``gate_up_scale`` / ``down_q`` / ``down_scale`` take their place in
+        ``w`` (so ``num_bytes`` counts what is resident), ``mlp_q[i]`` holds them for ``mlp``."""
+        if self.cfg.arch != "llama":
+            raise ValueError(f"mlp_dtype='fp8' quantises the dense Llama MLP; {self.cfg.name} has none "
+                             "(Mixtral's experts: dtype='fp8')")
+        if self.mlp_dtype == "fp8":
+            return self
+        for i in range(self.cfg.num_layers):
+            p = f"layers.{i}."
+            gu = self.w.pop(p + "gate_up")
+            if gu is None:                        # kept only fragment-tiled (ops.gemm.TILED_ONLY)
+                gu = untile_weight(self.wt[p + "gate_up"])
+            q = ops.quantize_dense_mlp(gu, self.w.pop(p + "down"))
+            del gu
+            self.wt.pop(p + "gate_up", None)
+            self.wt.pop(p + "down", None)
+            self.w[p + "gate_up_q"], self.w[p + "gate_up_scale"] = q.gate_up_q, q.gate_up_s
+            self.w[p + "down_q"], self.w[p + "down_scale"] = q.down_q, q.down_s
+            self.mlp_q[i] = q
+        self.mlp_dtype = "fp8"
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()              # the KV pool is sized from the device's free memory
+        return self
+
     def num_bytes(self) -> int:
         b = sum(t.numel() * t.element_size() for t in self.w.values() if t is not None)
         return b + sum(self.wt[n].numel() * self.wt[n].element_size() for n, t in self.w.items()
@@ -230,6 +260,13 @@ class DecoderModel:
             fuse_residual: Optional[torch.Tensor] = None, row_slot: Optional[torch.Tensor] = None,
             lora=None) -> torch.Tensor:
         p = f"layers.{i}."
+        if self.mlp_dtype == "fp8":
+            # W8A8 (ops.fp8_dense): decode sizes return split-K slabs at TP=1 like the bf16 down GEMM;
+            # no residual epilogue (the consumer's add + RMSNorm adds it)
+            out, a = ops.mlp_fp8(h, self.mlp_q[i], slabs=self.tp_size == 1)
+            if row_slot is not None:
+                out = self._lora_delta(out, a, i, "down", row_slot, lora)
+            return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out
         w = self.w[p + "gate_up"]
         if w is None:                             # kept only fragment-tiled (ops.gemm.TILED_ONLY)
             wt = self.wt[p + "gate_up"]

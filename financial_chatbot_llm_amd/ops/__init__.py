@@ -22,6 +22,8 @@ from . import lora
 from .lora import LoRATable, lora_delta
 from . import kv_tier
 from .kv_tier import gather_blocks, scatter_blocks
+from . import fp8_dense
+from .fp8_dense import DenseFp8MLP, dense_fp8_gemm, dense_fp8_reference, mlp_fp8, quantize_dense_mlp
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
            "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",

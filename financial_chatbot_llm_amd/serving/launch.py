@@ -72,6 +72,9 @@ def parse(argv=None):
                     help="KV pool element type (fp8: e4m3, twice the tokens in the same memory; TP = CP = 1)")
     ap.add_argument("--kv-scales", default=os.environ.get("PENNY_KV_SCALES") or None,
                     help="fp8 KV scales file (safetensors: k_scale, v_scale [layers, kv heads])")
+    ap.add_argument("--mlp-dtype", default=os.environ.get("PENNY_MLP_DTYPE", "bf16"),
+                    help="dense Llama MLP weights: bf16 | fp8 (e4m3 codes + row scales, per-row fp8 activations: "
+                         "half the MLP weight bytes; Mixtral's experts take PENNY_DTYPE=fp8)")
     ap.add_argument("--host-kv-gb", type=float, default=None,
                     help="GB of pinned host memory behind the KV pool: evicted prefix blocks are restored over "
                          "PCIe instead of recomputed (PENNY_HOST_KV_GB; 0: off; TP = CP = 1)")
@@ -169,7 +172,7 @@ def main(argv=None) -> int:
     cp_follower = ps.cp_size > 1 and ps.cp_rank != 0
     ecfg = config.EngineConfig.from_env(model=args.model, tp_size=args.tp, max_model_len=args.max_model_len,
                                         device=dev_type, use_cuda_graph=dev_type == "cuda", cp_size=args.cp,
-                                        kv_dtype=args.kv_dtype, kv_scales=args.kv_scales,
+                                        kv_dtype=args.kv_dtype, kv_scales=args.kv_scales, mlp_dtype=args.mlp_dtype,
                                         **({"host_kv_gb": args.host_kv_gb} if args.host_kv_gb is not None else {}),
                                         # a CP follower never decodes: a token KV pool, no graphs
                                         **({"num_kv_blocks": 16} if cp_follower else {}))

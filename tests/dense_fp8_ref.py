@@ -1,0 +1,293 @@
+"""Host-side cases and references for the dense fp8 GEMM (``gemm_fp8_dense.hip``,
+``ops.fp8_dense.dense_fp8_gemm``), in the style of ``decode_gemm_ref`` and ``moe_ref``.
+
+``moe_ref`` records that the fp8 MFMAs accumulate in something narrower than f32, so the exact cases
+use inputs that are exact under ANY accumulation width:
+
+* one-hot rows: row m of Xq is zero except a power of two at column k(m), W random e4m3 codes, xs and
+  ws powers of two -- Y[m, n] = W[n, k(m)] * x * xs[m] * ws[n] with a 4-bit significand;
+* few-term sums: at most 4 non-zeros per row in distinct 128-column chunks (distinct K slices where the
+  config has that many), integers of magnitude <= 8 on both sides: |sum| <= 256 < 2^9.
+
+Every case lives in buffers that hold more than the kernel may touch: Xq / xs rows >= M are NaN codes,
+Xq's row stride is padded (NaN bytes), and the outputs sit in sentinel-filled buffers with padded row
+strides and a tail.  ``emulate`` is a plain torch model of the kernel's contract, used on the CPU to
+check the exact expectations against an independent computation; the arithmetic certificate for
+random inputs is ``reference_f64``.
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Optional, Tuple
+
+import torch
+
+from moe_ref import U, UB, acc_bound
+
+FP8 = torch.float8_e4m3fn
+NAN_CODE = 0x7F                    # e4m3fn NaN (0xFF is the other one)
+XPAD_ROWS, XPAD_COLS = 3, 16       # NaN rows past M and NaN bytes past K in Xq
+YPAD_COLS = 8                      # sentinel columns past the output width (keeps 16-B row strides)
+TAIL = 64                          # sentinel elements past the last output row
+SENTINEL = -12352.0                # exact in bf16 and f32; never a result of the cases here
+
+
+def required_columns(K: int, S: int) -> List[int]:
+    """The columns k(m) the one-hot cases must hit: every column of the first and the last 128-column
+    step (so both halves of every 16-byte lane chunk, and every lane group), and one column either side
+    of every boundary between K slices and between the 128-column chunks the waves alternate on."""
+    cols = set(range(0, 128)) | set(range(K - 128, K))
+    for b in list(range(128, K, 128)) + [s * (K // S) for s in range(1, S)]:
+        cols |= {b - 1, b}
+    return sorted(cols)
+
+
+def codes_of(v: torch.Tensor) -> torch.Tensor:
+    """Exactly representable values -> e4m3 codes (uint8)."""
+    q = v.to(torch.float32).to(FP8)
+    assert torch.equal(q.float(), v.to(torch.float32)), "value not exact in e4m3"
+    return q.view(torch.uint8)
+
+
+def values_of(codes: torch.Tensor) -> torch.Tensor:
+    return codes.contiguous().view(FP8).float()
+
+
+def pow2(shape, lo: int, hi: int, g: torch.Generator) -> torch.Tensor:
+    return torch.exp2(torch.randint(lo, hi + 1, shape, generator=g).float())
+
+
+class Case(NamedTuple):
+    M: int
+    N: int
+    K: int
+    xq: torch.Tensor          # uint8 [M + XPAD_ROWS, K + XPAD_COLS]; rows >= M and columns >= K are NaN codes
+    xs: torch.Tensor          # f32 [M + XPAD_ROWS]; rows >= M NaN
+    wq: torch.Tensor          # uint8 [N, K]
+    ws: torch.Tensor          # f32 [N]
+
+    def to(self, dev) -> "Case":
+        return Case(self.M, self.N, self.K, *(t.to(dev) for t in (self.xq, self.xs, self.wq, self.ws)))
+
+    def x_view(self) -> torch.Tensor:
+        """[M + XPAD_ROWS, K] view with the padded row stride (what the kernel is given)."""
+        return self.xq[:, :self.K]
+
+
+def _wrap(M: int, N: int, K: int, x: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor) -> Case:
+    xq = torch.full((M + XPAD_ROWS, K + XPAD_COLS), NAN_CODE, dtype=torch.uint8)
+    xq[:M, :K] = x
+    xsf = torch.full((M + XPAD_ROWS,), float("nan"), dtype=torch.float32)
+    xsf[:M] = xs
+    return Case(M, N, K, xq, xsf, wq.contiguous(), ws.contiguous())
+
+
+def random_w_codes(N: int, K: int, g: torch.Generator) -> torch.Tensor:
+    """Random e4m3 codes, every finite value (subnormals, both zeros) included, no NaN."""
+    c = torch.randint(0, 256, (N, K), generator=g, dtype=torch.int32).to(torch.uint8)
+    c[(c & 0x7F) == NAN_CODE] = 0
+    return c
+
+
+def onehot_case(M: int, N: int, K: int, cols: torch.Tensor, seed: int, wq: Optional[torch.Tensor] = None) -> Case:
+    """Row m: +-2^a (a in -2..2) at column cols[m], zero elsewhere."""
+    g = torch.Generator().manual_seed(seed)
+    val = pow2((M,), -2, 2, g) * (1.0 - 2.0 * torch.randint(0, 2, (M,), generator=g).float())
+    x = torch.zeros((M, K), dtype=torch.uint8)
+    x[torch.arange(M), cols.long()] = codes_of(val)
+    if wq is None:
+        wq = random_w_codes(N, K, g)
+    return _wrap(M, N, K, x, pow2((M,), -3, 3, g), wq, pow2((N,), -3, 3, g))
+
+
+def onehot_cases(M: int, N: int, K: int, S: int, seed: int, dev="cpu", wq: Optional[torch.Tensor] = None) -> List[Case]:
+    """The one-hot calls that together hit every column of :func:`required_columns` (K, S): call c, row m
+    has its +-2^a at the (c M + m)-th required column (wrapping round).  Built at once and moved to
+    ``dev`` once; the cases are views, sharing W (``wq``: codes already on ``dev``) and ws."""
+    g = torch.Generator().manual_seed(seed)
+    cols = required_columns(K, S)
+    C = -(-len(cols) // M)
+    idx = torch.tensor((cols * 2)[:C * M]).view(C, M)
+    val = pow2((C, M), -2, 2, g) * (1.0 - 2.0 * torch.randint(0, 2, (C, M), generator=g).float())
+    xq = torch.full((C, M + XPAD_ROWS, K + XPAD_COLS), NAN_CODE, dtype=torch.uint8)
+    xq[:, :M, :K] = 0
+    xq[torch.arange(C)[:, None], torch.arange(M)[None, :], idx] = codes_of(val)
+    xs = torch.full((C, M + XPAD_ROWS), float("nan"), dtype=torch.float32)
+    xs[:, :M] = pow2((C, M), -3, 3, g)
+    if wq is None:
+        wq = random_w_codes(N, K, g)
+    ws = pow2((N,), -3, 3, g)
+    xq, xs, wq, ws = xq.to(dev), xs.to(dev), wq.to(dev).contiguous(), ws.to(dev)
+    return [Case(M, N, K, xq[c], xs[c], wq, ws) for c in range(C)]
+
+
+def int_w_codes(N: int, K: int, seed: int) -> torch.Tensor:
+    g = torch.Generator().manual_seed(seed)
+    return codes_of(torch.randint(-8, 9, (N, K), generator=g).float())
+
+
+def few_term_case(M: int, N: int, K: int, S: int, seed: int, wq: Optional[torch.Tensor] = None,
+                  silu: bool = False) -> Case:
+    """Row m: up to 4 integers (1..8, either sign) in distinct 128-column chunks -- spread over the K
+    slices first (one per slice while there are slices left), W integers in -8..8.  ``silu``: scales
+    that put the gate values in SiLU's curved range (|g| up to ~8)."""
+    g = torch.Generator().manual_seed(seed)
+    nch = K // 128
+    J = min(4, nch)
+    x = torch.zeros((M, K), dtype=torch.float32)
+    per = nch // S                                   # chunks per slice
+    for m in range(M):
+        order = torch.randperm(S, generator=g).tolist()
+        chunks = []
+        while len(chunks) < J:                       # round-robin over the slices, a fresh chunk each time
+            for s in order:
+                c = s * per + int(torch.randint(0, per, (1,), generator=g))
+                if c not in chunks and len(chunks) < J:
+                    chunks.append(c)
+        for c in chunks:
+            k = c * 128 + int(torch.randint(0, 128, (1,), generator=g))
+            v = int(torch.randint(1, 9, (1,), generator=g)) * (1 if int(torch.randint(0, 2, (1,), generator=g)) else -1)
+            x[m, k] = v
+    if wq is None:
+        wq = int_w_codes(N, K, seed + 1)
+    lo, hi = (-4, -2) if silu else (-3, 3)
+    return _wrap(M, N, K, codes_of(x), pow2((M,), lo, hi, g), wq, pow2((N,), -2 if silu else -3, 0 if silu else 3, g))
+
+
+def random_case(M: int, N: int, K: int, seed: int) -> Case:
+    """N(0, 1) values rounded to e4m3 on both sides, random positive f32 scales."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((M, K), generator=g).clamp(-400, 400).to(FP8).view(torch.uint8)
+    w = torch.randn((N, K), generator=g).clamp(-400, 400).to(FP8).view(torch.uint8)
+    xs = torch.rand((M,), generator=g) * 0.02 + 0.001
+    ws = torch.rand((N,), generator=g) * 0.02 + 0.001
+    return _wrap(M, N, K, x, xs, w, ws)
+
+
+# ---------------------------------------------------------------------------------------------
+# outputs inside sentinel buffers
+# ---------------------------------------------------------------------------------------------
+class OutBuf(NamedTuple):
+    flat: torch.Tensor        # the whole allocation
+    view: torch.Tensor        # what the kernel is given: [M, ldy] (bf16) or [S, M, ldy] (f32) rows of it
+    width: int                # columns the kernel may write per row
+
+
+def out_buffer(M: int, N: int, epilogue: str, S: int, dev) -> OutBuf:
+    width = N // 2 if epilogue == "silu" else N
+    ldy = width + YPAD_COLS
+    rows = (S if epilogue == "slabs" else 1) * M
+    dt = torch.float32 if epilogue == "slabs" else torch.bfloat16
+    flat = torch.full((rows * ldy + TAIL,), SENTINEL, dtype=dt, device=dev)
+    v = flat[:rows * ldy].view(rows, ldy)
+    return OutBuf(flat, v.view(S, M, ldy) if epilogue == "slabs" else v, width)
+
+
+def bits(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def untouched(buf: OutBuf) -> bool:
+    """Every element outside the [.., :width] columns of the rows, and the tail, still the sentinel."""
+    ref = torch.full_like(buf.flat, SENTINEL)
+    got = buf.flat.clone()
+    got[:buf.view.numel()].view(buf.view.shape)[..., :buf.width] = SENTINEL
+    return torch.equal(bits(got), bits(ref))
+
+
+def result(buf: OutBuf) -> torch.Tensor:
+    return buf.view[..., :buf.width]
+
+
+# ---------------------------------------------------------------------------------------------
+# expectations
+# ---------------------------------------------------------------------------------------------
+def exact_product(case: Case, S: int) -> torch.Tensor:
+    """f32 [S, M, N]: slice s of (Xq x Wq^T) * xs * ws for a case whose sums are exact in f32 (sparse
+    rows: computed from the non-zero columns alone, on the case's device).  -0 becomes +0, as a sum
+    that starts from +0 gives."""
+    M, N, K = case.M, case.N, case.K
+    x = values_of(case.xq[:M, :K].contiguous())
+    w = values_of(case.wq)
+    P = torch.zeros((S, M, N), dtype=torch.float32, device=x.device)
+    nz = (x != 0).nonzero()
+    J = int((x != 0).sum(1).max()) if nz.numel() else 0
+    kc = K // S
+    for j in range(J):                                # the j-th non-zero of every row that has one
+        cnt = (x != 0).cumsum(1)
+        sel = (x != 0) & (cnt == j + 1)
+        rows, cols = sel.nonzero(as_tuple=True)
+        term = w[:, cols].t() * x[rows, cols][:, None]            # [rows, N]
+        P.index_put_((cols // kc, rows), term, accumulate=True)
+    P = P * case.xs[:M].float()[None, :, None] * case.ws.float()[None, None, :]
+    return P + 0.0
+
+
+def expected(case: Case, epilogue: str, S: int, silu_mul) -> torch.Tensor:
+    """The bit-exact expectation of an exact case: f32 slabs; the sum rounded once to bf16; or
+    ``silu_mul(interleave16=True)`` (the ops entry, passed in) of that bf16 gate|up."""
+    P = exact_product(case, S)
+    if epilogue == "slabs":
+        return P
+    y = P.sum(0).to(torch.bfloat16)                   # exact sum (integers / one term), one rounding
+    return silu_mul(y, interleave16=True) if epilogue == "silu" else y
+
+
+def emulate(case: Case, epilogue: str, S: int, silu_mul) -> torch.Tensor:
+    """Plain torch model of the kernel's contract on rows < M (f32 matmul per K slice): what the CPU
+    self-check compares the exact expectations with."""
+    M, N, K = case.M, case.N, case.K
+    x = values_of(case.xq[:M, :K].contiguous()).view(M, S, K // S).transpose(0, 1)
+    w = values_of(case.wq).view(N, S, K // S).transpose(0, 1)
+    P = torch.einsum("smk,snk->smn", x.double(), w.double()).float()
+    P = P * case.xs[:M].float()[None, :, None] * case.ws.float()[None, None, :] + 0.0
+    if epilogue == "slabs":
+        return P
+    y = P.sum(0).to(torch.bfloat16)
+    return silu_mul(y, interleave16=True) if epilogue == "silu" else y
+
+
+class F64Ref(NamedTuple):
+    ref: torch.Tensor         # f64, CPU: [S, M, N] (slabs), [M, N] (bf16) or [M, N/2] (silu)
+    bound: torch.Tensor       # same shape
+    ssc: Optional[torch.Tensor]   # S |scale| per element (bf16 / slabs): moe_ref.acc_units' third argument
+
+
+def reference_f64(case: Case, epilogue: str, S: int) -> F64Ref:
+    """f64 reference of the kernel's own Xq and xs with ``moe_ref``'s certificate: the dot product of
+    each element is within ``acc_bound(K) * S_abs`` (S_abs = sum |x| |w| over the element's K slice)
+    plus its output roundings -- slabs: two scale products (3 U); bf16: those and the one bf16 rounding
+    (UB + 3 U); silu: ``moe_ref.gemm1_silu_ref``'s propagation through bf16(g), bf16(u), bf16(silu(g))
+    and the product.  The matmuls run in f64 on the case's device."""
+    M, N, K = case.M, case.N, case.K
+    x = values_of(case.xq[:M, :K].contiguous()).double().view(M, S, K // S).transpose(0, 1)
+    w = values_of(case.wq).double().view(N, S, K // S).transpose(0, 1)
+    acc = torch.bmm(x, w.transpose(1, 2))                          # [S, M, N]
+    sab = torch.bmm(x.abs(), w.abs().transpose(1, 2))
+    sc = case.xs[:M].double()[None, :, None] * case.ws.double()[None, None, :]
+    y, ssc = (acc * sc).cpu(), (sab * sc.abs()).cpu()
+    eb = acc_bound(K) * ssc
+    if epilogue == "slabs":
+        return F64Ref(y, eb + y.abs() * 3 * U, ssc)
+    y, eb, ssc = y[0], eb[0], ssc[0]
+    if epilogue == "bf16":
+        return F64Ref(y, eb + y.abs() * (UB + 3 * U), ssc)
+    F_ = N // 2
+    gu = y.view(M, F_ // 16, 2, 16)
+    e = (eb + y.abs() * (UB + 3 * U)).view(M, F_ // 16, 2, 16)
+    g, u = gu[:, :, 0].reshape(M, F_), gu[:, :, 1].reshape(M, F_)
+    e_g, e_u = e[:, :, 0].reshape(M, F_), e[:, :, 1].reshape(M, F_)
+    sl = g * torch.sigmoid(g)
+    e_s = 1.1 * e_g + (sl.abs() + 1.1 * e_g) * (UB + (8.0 + g.abs()) * U)
+    e_p = e_s * (u.abs() + e_u) + sl.abs() * e_u
+    return F64Ref(sl * u, e_p + ((sl * u).abs() + e_p) * (UB + 2 * U), None)
+
+
+def table_splits(N: int, K: int) -> List[Tuple[int, int]]:
+    """(S, ntf) of every table entry for (N, K) in ``ops.fp8_dense.DENSE_FP8``, plus S = 1."""
+    from financial_chatbot_llm_amd.ops.fp8_dense import DENSE_FP8
+    out = []
+    for _, S, ntf in DENSE_FP8.get((N, K), ()):
+        for c in ((S, ntf), (1, ntf)):
+            if c not in out:
+                out.append(c)
+    return out
