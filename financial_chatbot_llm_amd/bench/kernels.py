@@ -2353,6 +2353,137 @@ def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128
     return out
 
 
+def bench_dense_mxfp4_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128, 256, 512, 2048),
+                          sweep: bool = False) -> List[Dict]:
+    """One dense Llama MLP with MXFP4 weights (``ops.mlp_mxfp4``: the 4-bit streaming kernel up to 256 rows,
+    the e4m3 expansion + the fp8 kernels above; the row-quantisation passes and the expansion included)
+    against fp8 (``ops.mlp_fp8``) and bf16 (``linear`` as ``DecoderModel.mlp`` calls it), the three taking
+    turns in one process, each format's weights rotated over copies so every call streams W from HBM.
+    Reports the three times, the winner, and for the mxfp4 path each stage alone with the TB/s of the W bytes
+    it reads (codes + exponents).  ``sweep``: instead, every (S, ntf) candidate of the 4-bit kernel per GEMM
+    and M <= 256 (the numbers ``ops.mxfp4_dense.DENSE_MXFP4`` is chosen from)."""
+    from ..ops import fp8_dense, gemm, mxfp4_dense
+    out = []
+    g = torch.Generator(device=dev).manual_seed(0)
+    for model in models:
+        H, F_, tuning = DENSE_FP8_MODELS[model]
+        shard = model.endswith("tp8")
+        if tuning:
+            gemm.load_gemm_tuning(tuning)
+        copies = max(2, -(-(768 << 20) // (3 * H * F_)))
+        bcopies = max(2, -(-(768 << 20) // (6 * H * F_)))
+        mcopies = max(2, -(-(768 << 20) // (3 * H * F_ // 2)))
+        q, bw, m4 = [], [], []
+        scratch = mxfp4_dense.ExpandScratch(H, F_, dev)
+        for c in range(max(copies, bcopies, mcopies)):
+            gu = (torch.randn((2 * F_, H), device=dev, generator=g) * 0.02).to(torch.bfloat16)
+            dn = (torch.randn((H, F_), device=dev, generator=g) * 0.02).to(torch.bfloat16)
+            m4.append(mxfp4_dense.quantize_dense_mlp_mxfp4(gu, dn, scratch=scratch))
+            if c < copies and not sweep:
+                q.append(fp8_dense.quantize_dense_mlp(gu, dn))
+            if c < bcopies and not sweep:
+                ent = {"gu": gu, "dn": dn, "gut": None, "dnt": None}
+                if gemm.uses_tiled_weight(2 * F_, H):
+                    ent["gut"] = gemm.tile_weight(gu)
+                    if gemm.tiled_only(2 * F_, H):
+                        ent["gu"] = None
+                if gemm.uses_tiled_weight(H, F_):
+                    ent["dnt"] = gemm.tile_weight(dn)
+                bw.append(ent)
+            del gu, dn
+        mcopies = len(m4)
+        it = [0]
+
+        def nxt(n):
+            it[0] += 1
+            return it[0] % n
+
+        def bf16_mlp(h):
+            e = bw[nxt(bcopies)]
+            if e["gu"] is None:
+                a = gemm.linear_tiled(h, e["gut"], 2 * F_, epilogue="silu")
+            else:
+                a = gemm.linear(h, e["gu"], epilogue="silu", wt=e["gut"])
+            return gemm.linear(a, e["dn"], wt=e["dnt"], slabs=not shard)
+
+        wbytes = lambda N_, K_: N_ * K_ // 2 + N_ * K_ // 32      # noqa: E731
+        for M in Ms:
+            h = torch.randn((M, H), device=dev, generator=g).to(torch.bfloat16)
+            xq, xs = fp8_dense._quant(h)
+            if sweep:
+                if M > mxfp4_dense.MAX_M:
+                    continue
+                a = torch.randn((M, F_), device=dev, generator=g).to(torch.bfloat16)
+                aq, as_ = fp8_dense._quant(a)
+                for name, (N_, K_), x_, s_, epi in (("gate_up", (2 * F_, H), xq, xs, "silu"),
+                                                    ("down", (H, F_), aq, as_, "bf16" if shard else "slabs")):
+                    fns = {}
+                    for ntf in (2, 4):
+                        for S in ((1, 2, 4, 7, 8, 14, 16) if epi == "slabs" else (1,)):
+                            if K_ % (256 * S) or N_ % (16 * ntf) or (N_ // (16 * ntf)) * S > 4096:
+                                continue
+                            ws_ = [(w.gate_up_c, w.gate_up_e, w.gate_up_s) if name == "gate_up" else
+                                   (w.down_c, w.down_e, w.down_s) for w in m4]
+                            fns[f"S{S}_ntf{ntf}"] = (lambda S=S, ntf=ntf, ws_=ws_, x_=x_, s_=s_, epi=epi:
+                                                     mxfp4_dense.dense_mxfp4_gemm(x_, s_, *ws_[nxt(mcopies)], epi, S, ntf))
+                    t = _timeit_interleaved(fns, iters=2 * mcopies, rounds=5)
+                    best = min(t, key=t.get)
+                    row = {"bench": "dense_mxfp4_sweep", "model": model, "M": M, name: {"shape": [N_, K_]}, "epi": epi,
+                           "us": {k: round(v, 1) for k, v in t.items()}, "best": best,
+                           "best_TBps": round(wbytes(N_, K_) / t[best] / 1e6, 2)}
+                    out.append(row)
+                    print(json.dumps(row), flush=True)
+                continue
+            path = mxfp4_dense.mlp_mxfp4_path(h, m4[0])
+            fns = {"mxfp4": lambda: mxfp4_dense.mlp_mxfp4(h, m4[nxt(mcopies)], slabs=not shard),
+                   "fp8": lambda: fp8_dense.mlp_fp8(h, q[nxt(copies)], slabs=not shard), "bf16": lambda: bf16_mlp(h)}
+            t = _timeit_interleaved(fns, iters=2 * max(copies, bcopies, mcopies))
+            row = {"bench": "dense_mxfp4_mlp", "model": model, "M": M, "path": path, "mxfp4_us": round(t["mxfp4"], 1),
+                   "fp8_us": round(t["fp8"], 1), "bf16_us": round(t["bf16"], 1),
+                   "speedup_vs_bf16": round(t["bf16"] / t["mxfp4"], 2), "speedup_vs_fp8": round(t["fp8"] / t["mxfp4"], 2),
+                   "winner": min(t, key=t.get)}
+            # the mxfp4 path's stages alone
+            _, a = mxfp4_dense.mlp_mxfp4(h, m4[0])
+            aq, as_ = fp8_dense._quant(a)
+            parts = {"quant_h": lambda: fp8_dense._quant(h), "quant_a": lambda: fp8_dense._quant(a)}
+            if path == "stream":
+                _, ntf1 = mxfp4_dense.dense_mxfp4_config(M, 2 * F_, H, "silu")
+                epi2 = "bf16" if shard else "slabs"
+                S2, ntf2 = mxfp4_dense.dense_mxfp4_config(M, H, F_, epi2)
+
+                def g1():
+                    w = m4[nxt(mcopies)]
+                    mxfp4_dense.dense_mxfp4_gemm(xq, xs, w.gate_up_c, w.gate_up_e, w.gate_up_s, "silu", 1, ntf1)
+
+                def g2():
+                    w = m4[nxt(mcopies)]
+                    mxfp4_dense.dense_mxfp4_gemm(aq, as_, w.down_c, w.down_e, w.down_s, epi2, S2, ntf2)
+                parts.update(gate_up=g1, down=g2)
+                cfgs = {"gate_up": [1, ntf1], "down": [S2, ntf2]}
+            else:
+                def ex():
+                    w = m4[nxt(mcopies)]
+                    mxfp4_dense.expand_mxfp4(w.gate_up_c, w.gate_up_e, out=scratch.gate_up)
+                    mxfp4_dense.expand_mxfp4(w.down_c, w.down_e, out=scratch.down)
+                parts["expand"] = ex
+                cfgs = {"gate_up": "expand + fp8", "down": "expand + fp8"}
+            pt = _timeit_interleaved(parts, iters=2 * mcopies, rounds=5)
+            for name, (N_, K_) in (("gate_up", (2 * F_, H)), ("down", (H, F_))):
+                row[name] = {"shape": [N_, K_], "cfg": cfgs[name]}
+                if name in pt:
+                    row[name].update(us=round(pt[name], 1), W_TBps=round(wbytes(N_, K_) / pt[name] / 1e6, 2))
+            row["quant_us"] = [round(pt["quant_h"], 1), round(pt["quant_a"], 1)]
+            if "expand" in pt:
+                # reads 17/32 of a byte and writes one byte per weight
+                row["expand_us"] = round(pt["expand"], 1)
+                row["expand_TBps"] = round((wbytes(3 * F_, H) + 3 * F_ * H) / pt["expand"] / 1e6, 2)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+        del q, bw, m4, scratch
+        torch.cuda.empty_cache()
+    return out
+
+
 def interleave16_rows(w: torch.Tensor) -> torch.Tensor:
     from ..ops.gemm import interleave16
     half = w.shape[0] // 2
@@ -2398,6 +2529,8 @@ def main(argv=None) -> int:
                 "kv_tier": bench_kv_tier,
                 "dense_fp8_mlp": bench_dense_fp8_mlp,
                 "dense_fp8_sweep": lambda d: bench_dense_fp8_mlp(d, Ms=(1, 16, 64, 128, 256), sweep=True),
+                "dense_mxfp4_mlp": bench_dense_mxfp4_mlp,
+                "dense_mxfp4_sweep": lambda d: bench_dense_mxfp4_mlp(d, Ms=(1, 16, 64, 128, 256), sweep=True),
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),

@@ -134,8 +134,10 @@ class EngineConfig:
     kv_scales: Optional[str] = None
     # dense Llama MLP weights (gate|up, down): "bf16" | "fp8" (OCP e4m3fn codes + one f32 scale per
     # output row, dynamic per-row e4m3 activations: half the MLP's weight bytes resident and streamed
-    # per decode step; ops/fp8_dense.py).  Mixtral's experts take dtype="fp8" instead.  The default is
-    # read from PENNY_MLP_DTYPE when the config is constructed.
+    # per decode step; ops/fp8_dense.py) | "mxfp4" (OCP e2m1 codes, one E8M0 exponent per 32 columns and
+    # one f32 scale per row, the same activations: a quarter of the bytes, about four times fp8's weight
+    # error; ops/mxfp4_dense.py).  Mixtral's experts take dtype="fp8" instead.  The default is read from
+    # PENNY_MLP_DTYPE when the config is constructed.
     mlp_dtype: str = field(default_factory=lambda: os.getenv("PENNY_MLP_DTYPE", "bf16"))
     # of (free HBM after weights - 6 GiB); 0.92 leaves ~20 GiB of the 288 GiB unused at the end of
     # the 20/5 bench (engine stats hbm_used_gib: 8B 264.5, Mixtral fp8 267.9; 0.95 measured no
@@ -195,8 +197,8 @@ class EngineConfig:
 
     def __post_init__(self):
         self.check_host_kv()
-        if self.mlp_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"unknown mlp_dtype {self.mlp_dtype!r} (bf16 | fp8; PENNY_MLP_DTYPE)")
+        if self.mlp_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"unknown mlp_dtype {self.mlp_dtype!r} (bf16 | fp8 | mxfp4; PENNY_MLP_DTYPE)")
 
     def check_host_kv(self) -> None:
         """ValueError naming the cause when the host KV tier is on in a form it does not support."""

@@ -11,10 +11,10 @@ def build_model(engine_cfg, device, seed: int = 0):
     from .mixtral import MixtralModel
     cfg = get_model_config(engine_cfg.model)
     mlp_dtype = getattr(engine_cfg, "mlp_dtype", "bf16")
-    if mlp_dtype not in ("bf16", "fp8"):
-        raise ValueError(f"unknown mlp_dtype {mlp_dtype!r} (bf16 | fp8)")
-    if mlp_dtype == "fp8" and cfg.arch != "llama":
-        raise ValueError(f"mlp_dtype='fp8' quantises the dense Llama MLP; {cfg.name} has none "
+    if mlp_dtype not in ("bf16", "fp8", "mxfp4"):
+        raise ValueError(f"unknown mlp_dtype {mlp_dtype!r} (bf16 | fp8 | mxfp4)")
+    if mlp_dtype != "bf16" and cfg.arch != "llama":
+        raise ValueError(f"mlp_dtype={mlp_dtype!r} quantises the dense Llama MLP; {cfg.name} has none "
                          "(Mixtral's experts: dtype='fp8')")
     if cfg.arch == "mixtral":
         model = MixtralModel(cfg, device=device, fp8=getattr(engine_cfg, "dtype", "bf16") == "fp8",
@@ -36,6 +36,8 @@ def build_model(engine_cfg, device, seed: int = 0):
         model.init_random(seed=engine_cfg.seed if hasattr(engine_cfg, "seed") else seed)
     if mlp_dtype == "fp8":
         model.quantize_mlp()                  # this rank's bf16 gate|up / down shards -> e4m3 + row scales
+    elif mlp_dtype == "mxfp4":
+        model.quantize_mlp("mxfp4")           # -> e2m1 codes + E8M0 block exponents + row scales
     return model
 
 

@@ -84,7 +84,8 @@ class DecoderModel:
         # per-request LoRA adapters (ops.lora): a step whose metadata carries ``row_slot`` adds the rows'
         # deltas to QKV, O and down from the metadata's table, else from this one (None: no table)
         self.lora: Optional["ops.LoRATable"] = None
-        # dense MLP weights: "bf16", or "fp8" once quantize_mlp() replaced them by ops.DenseFp8MLP holders
+        # dense MLP weights: "bf16", or "fp8" / "mxfp4" once quantize_mlp() replaced them by ops.DenseFp8MLP /
+        # ops.DenseMxfp4MLP holders
         self.mlp_dtype = "bf16"
         self.mlp_q: Dict[int, "ops.DenseFp8MLP"] = {}
         self.cos_sin = ops.rope_cos_sin(self.D, cfg.max_position, cfg.rope_theta, cfg.rope_scaling,
@@ -209,29 +210,52 @@ class DecoderModel:
         self.w[name] = buf[:rows]
         self._lm_pad = buf
 
-    def quantize_mlp(self) -> "DecoderModel":
-        """bf16 gate|up and down of every layer -> fp8 e4m3 codes + f32 row scales (``ops.fp8_dense``),
-        quantised from this rank's shard; the bf16 weights and their fragment-tiled copies are dropped.
-        ``layers.i.gate_up_q`` / ``gate_up_scale`` / ``down_q`` / ``down_scale`` take their place in
+    def quantize_mlp(self, dtype: str = "fp8") -> "DecoderModel":
+        """bf16 gate|up and down of every layer -> ``dtype`` "fp8": e4m3 codes + f32 row scales
+        (``ops.fp8_dense``), or "mxfp4": e2m1 codes + E8M0 block exponents + f32 row scales
+        (``ops.mxfp4_dense``), quantised from this rank's shard; the bf16 weights and their fragment-tiled
+        copies are dropped.  ``layers.i.gate_up_q`` / ``gate_up_scale`` / ``down_q`` / ``down_scale`` (fp8)
+        or ``gate_up_c`` / ``gate_up_e`` / ``gate_up_scale`` / ``down_c`` / ``down_e`` / ``down_scale``
+        (mxfp4, with the one e4m3 expansion scratch all layers share above 256 rows) take their place in
         ``w`` (so ``num_bytes`` counts what is resident), ``mlp_q[i]`` holds them for ``mlp``."""
+        if dtype not in ("fp8", "mxfp4"):
+            raise ValueError(f"unknown mlp_dtype {dtype!r} for quantize_mlp (fp8 | mxfp4)")
         if self.cfg.arch != "llama":
-            raise ValueError(f"mlp_dtype='fp8' quantises the dense Llama MLP; {self.cfg.name} has none "
+            raise ValueError(f"mlp_dtype={dtype!r} quantises the dense Llama MLP; {self.cfg.name} has none "
                              "(Mixtral's experts: dtype='fp8')")
-        if self.mlp_dtype == "fp8":
+        if self.mlp_dtype == dtype:
             return self
+        if self.mlp_dtype != "bf16":
+            raise ValueError(f"the MLP is already quantised to mlp_dtype={self.mlp_dtype!r}; {dtype!r} needs the bf16 weights")
+        scratch = None
         for i in range(self.cfg.num_layers):
             p = f"layers.{i}."
             gu = self.w.pop(p + "gate_up")
             if gu is None:                        # kept only fragment-tiled (ops.gemm.TILED_ONLY)
                 gu = untile_weight(self.wt[p + "gate_up"])
-            q = ops.quantize_dense_mlp(gu, self.w.pop(p + "down"))
-            del gu
+            down = self.w.pop(p + "down")
             self.wt.pop(p + "gate_up", None)
             self.wt.pop(p + "down", None)
-            self.w[p + "gate_up_q"], self.w[p + "gate_up_scale"] = q.gate_up_q, q.gate_up_s
-            self.w[p + "down_q"], self.w[p + "down_scale"] = q.down_q, q.down_s
+            if dtype == "fp8":
+                q = ops.quantize_dense_mlp(gu, down)
+                self.w[p + "gate_up_q"], self.w[p + "gate_up_scale"] = q.gate_up_q, q.gate_up_s
+                self.w[p + "down_q"], self.w[p + "down_scale"] = q.down_q, q.down_s
+            else:
+                if scratch is None and self.device.type == "cuda":
+                    # one layer's e4m3 MLP for steps above 256 rows, allocated now: the KV pool is sized after it
+                    scratch = ops.mxfp4_dense.ExpandScratch(gu.shape[1], down.shape[1], self.device)
+                    self.w["mlp_expand.gate_up_q"], self.w["mlp_expand.down_q"] = scratch.gate_up, scratch.down
+                # down is sharded along its rows' columns: the row scale comes from the whole row (the maximum of
+                # the ranks' shard amax), so every rank holds the codes TP = 1 has in its columns
+                amax = None
+                if self.tp_size > 1 and comm.tp_size() == self.tp_size:
+                    amax = comm.tp_all_reduce_max(down.float().abs().amax(dim=1))
+                q = ops.quantize_dense_mlp_mxfp4(gu, down, scratch=scratch, down_row_amax=amax)
+                self.w[p + "gate_up_c"], self.w[p + "gate_up_e"], self.w[p + "gate_up_scale"] = q.gate_up_c, q.gate_up_e, q.gate_up_s
+                self.w[p + "down_c"], self.w[p + "down_e"], self.w[p + "down_scale"] = q.down_c, q.down_e, q.down_s
+            del gu, down
             self.mlp_q[i] = q
-        self.mlp_dtype = "fp8"
+        self.mlp_dtype = dtype
         if self.device.type == "cuda":
             torch.cuda.empty_cache()              # the KV pool is sized from the device's free memory
         return self
@@ -264,6 +288,12 @@ class DecoderModel:
             # W8A8 (ops.fp8_dense): decode sizes return split-K slabs at TP=1 like the bf16 down GEMM;
             # no residual epilogue (the consumer's add + RMSNorm adds it)
             out, a = ops.mlp_fp8(h, self.mlp_q[i], slabs=self.tp_size == 1)
+            if row_slot is not None:
+                out = self._lora_delta(out, a, i, "down", row_slot, lora)
+            return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out
+        if self.mlp_dtype == "mxfp4":
+            # W4A8 (ops.mxfp4_dense): the fp8 branch's outputs and consumers
+            out, a = ops.mlp_mxfp4(h, self.mlp_q[i], slabs=self.tp_size == 1)
             if row_slot is not None:
                 out = self._lora_delta(out, a, i, "down", row_slot, lora)
             return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out

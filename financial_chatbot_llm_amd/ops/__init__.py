@@ -24,6 +24,9 @@ from . import kv_tier
 from .kv_tier import gather_blocks, scatter_blocks
 from . import fp8_dense
 from .fp8_dense import DenseFp8MLP, dense_fp8_gemm, dense_fp8_reference, mlp_fp8, quantize_dense_mlp
+from . import mxfp4_dense
+from .mxfp4_dense import (DenseMxfp4MLP, dense_mxfp4_gemm, dense_mxfp4_reference, expand_mxfp4, mlp_mxfp4,
+                          quantize_dense_mlp_mxfp4, quantize_mxfp4_rowwise, unpack_mxfp4)
 
 __all__ = ["gelu_", "silu_mul", "KV_BS", "DecodeWorkspace", "decode", "default_scale", "prefill", "rope_cos_sin",
            "rope_kv_write", "write_kv_ref", "gather_kv_ref", "kv_dequant", "KVScales", "make_kv_scales", "embedding", "layer_norm", "rms_norm", "filtered_topk",

@@ -102,6 +102,8 @@ _SIGS = {
     "penny_silu_quant_rows_fp8": [P, c_int, c_int, P, P, P],
     "penny_moe_gemm_fp8": [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "penny_dense_fp8_gemm": [P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "penny_dense_mxfp4_gemm": [P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "penny_mxfp4_expand": [P, P, P, c_int, c_int, P],
     "penny_moe_combine": [P, P, c_int, c_int, c_int, P, P],
     "penny_moe_combine_weighted": [P, P, P, c_int, c_int, c_int, P, P],
     "penny_filtered_topk": [P, P, P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, P, c_int, P, P, P, P],

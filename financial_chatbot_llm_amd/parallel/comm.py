@@ -189,6 +189,15 @@ def tp_all_reduce(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def tp_all_reduce_max(x: torch.Tensor) -> torch.Tensor:
+    """Element-wise maximum of ``x`` over the TP group, in place (load-time use: RCCL / gloo, never the
+    custom sum kernel)."""
+    s = state()
+    if s.tp_size > 1:
+        dist.all_reduce(x, op=dist.ReduceOp.MAX, group=s.tp_group)
+    return x
+
+
 class _Done:
     def wait(self) -> None:
         return None

@@ -74,7 +74,8 @@ def parse(argv=None):
                     help="fp8 KV scales file (safetensors: k_scale, v_scale [layers, kv heads])")
     ap.add_argument("--mlp-dtype", default=os.environ.get("PENNY_MLP_DTYPE", "bf16"),
                     help="dense Llama MLP weights: bf16 | fp8 (e4m3 codes + row scales, per-row fp8 activations: "
-                         "half the MLP weight bytes; Mixtral's experts take PENNY_DTYPE=fp8)")
+                         "half the MLP weight bytes) | mxfp4 (e2m1 codes + block exponents + row scales: a quarter); "
+                         "Mixtral's experts take PENNY_DTYPE=fp8")
     ap.add_argument("--host-kv-gb", type=float, default=None,
                     help="GB of pinned host memory behind the KV pool: evicted prefix blocks are restored over "
                          "PCIe instead of recomputed (PENNY_HOST_KV_GB; 0: off; TP = CP = 1)")
