@@ -2226,17 +2226,28 @@ def _timeit_interleaved(fns: Dict[str, Callable[[], None]], iters: int, rounds: 
     return {k: statistics.median(v) for k, v in res.items()}
 
 
-def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128, 256, 512, 2048),
-                        sweep: bool = False) -> List[Dict]:
-    """One dense Llama MLP (gate|up + SiLU, down; the fp8 path's two row-quantisation passes included):
-    fp8 weights (``ops.mlp_fp8``) against bf16 (``linear`` as ``DecoderModel.mlp`` calls it, tiled copies
-    and slabs as the model would hold them), interleaved in one process, the weights rotated over
-    copies so every call streams W from HBM.  Reports both times, which one wins, and for the fp8 path
-    each GEMM alone with the TB/s of its W bytes.  The 70B TP=8 row is one rank's shard: down returns
-    bf16 for the all-reduce.  ``sweep``: instead, every (S, ntf) candidate of the streaming kernel per
-    GEMM and M <= 256 (the numbers ``ops.fp8_dense.DENSE_FP8`` is chosen from)."""
+def bench_dense_mlp(dev, fmt: str, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128, 256, 512, 2048),
+                    sweep: bool = False) -> List[Dict]:
+    """One dense Llama MLP (gate|up + SiLU, down; the row-quantisation passes included) with ``fmt`` "fp8"
+    (``ops.mlp_fp8``) or "mxfp4" (``ops.mlp_mxfp4``: the 4-bit streaming kernel up to 256 rows, the e4m3
+    expansion + the fp8 kernels above, the expansion included) weights against bf16 (``linear`` as
+    ``DecoderModel.mlp`` calls it, tiled copies and slabs as the model would hold them) -- and mxfp4 against
+    fp8 as well --, taking turns in one process, each format's weights rotated over copies so every call
+    streams W from HBM.  Reports the times, the winner, and for ``fmt``'s path each stage alone with the TB/s
+    of the W bytes it reads (mxfp4: codes + exponents).  The 70B TP=8 row is one rank's shard: down returns
+    bf16 for the all-reduce.  ``sweep``: instead, every (S, ntf) candidate of the format's streaming kernel
+    per GEMM and M <= 256 (the numbers ``DENSE_FP8`` / ``DENSE_MXFP4`` are chosen from)."""
     from ..ops import _native as N
-    from ..ops import fp8_dense, gemm
+    from ..ops import fp8_dense, gemm, mxfp4_dense
+    m4 = fmt == "mxfp4"
+    if m4:
+        chunk, config, dense_gemm = mxfp4_dense.CHUNK, mxfp4_dense.dense_mxfp4_config, mxfp4_dense.dense_mxfp4_gemm
+        mlp, mlp_path = mxfp4_dense.mlp_mxfp4, mxfp4_dense.mlp_mxfp4_path
+        wbytes = lambda N_, K_: N_ * K_ // 2 + N_ * K_ // 32      # noqa: E731
+    else:
+        chunk, config, dense_gemm = fp8_dense.CHUNK, fp8_dense.dense_fp8_config, fp8_dense.dense_fp8_gemm
+        mlp, mlp_path = fp8_dense.mlp_fp8, fp8_dense.mlp_fp8_path
+        wbytes = lambda N_, K_: N_ * K_                           # noqa: E731
     out = []
     g = torch.Generator(device=dev).manual_seed(0)
     for model in models:
@@ -2246,11 +2257,15 @@ def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128
             gemm.load_gemm_tuning(tuning)
         copies = max(2, -(-(768 << 20) // (3 * H * F_)))
         bcopies = max(2, -(-(768 << 20) // (6 * H * F_)))
-        q, bw = [], []
-        for c in range(max(copies, bcopies)):
+        ncopy = max(copies, bcopies, max(2, -(-(768 << 20) // (3 * H * F_ // 2))) if m4 else 0)
+        q, bw, w4 = [], [], []
+        scratch = mxfp4_dense.ExpandScratch(H, F_, dev) if m4 else None
+        for c in range(ncopy):
             gu = (torch.randn((2 * F_, H), device=dev, generator=g) * 0.02).to(torch.bfloat16)
             dn = (torch.randn((H, F_), device=dev, generator=g) * 0.02).to(torch.bfloat16)
-            if c < copies:
+            if m4:
+                w4.append(mxfp4_dense.quantize_dense_mlp_mxfp4(gu, dn, scratch=scratch))
+            if c < copies and not (m4 and sweep):
                 q.append(fp8_dense.quantize_dense_mlp(gu, dn))
             if c < bcopies and not sweep:
                 ent = {"gu": gu, "dn": dn, "gut": None, "dnt": None}
@@ -2262,6 +2277,10 @@ def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128
                     ent["dnt"] = gemm.tile_weight(dn)
                 bw.append(ent)
             del gu, dn
+        wq = w4 if m4 else q                     # the copies of ``fmt``'s weights, and each GEMM's tensors of them
+        wcopies = len(wq)
+        half = len(wq[0].tensors()) // 2
+        gus, dns = [w.tensors()[:half] for w in wq], [w.tensors()[half:] for w in wq]
         it = [0]
 
         def nxt(n):
@@ -2278,52 +2297,63 @@ def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128
 
         for M in Ms:
             h = torch.randn((M, H), device=dev, generator=g).to(torch.bfloat16)
+            xq, xs = fp8_dense._quant(h)
             if sweep:
                 if M > fp8_dense.MAX_M:
                     continue
-                xq, xs = fp8_dense._quant(h)
                 a = torch.randn((M, F_), device=dev, generator=g).to(torch.bfloat16)
                 aq, as_ = fp8_dense._quant(a)
-                for name, (N_, K_), x_, s_, epi in (("gate_up", (2 * F_, H), xq, xs, "silu"),
-                                                    ("down", (H, F_), aq, as_, "bf16" if shard else "slabs")):
+                for name, (N_, K_), x_, s_, ws_, epi in (("gate_up", (2 * F_, H), xq, xs, gus, "silu"),
+                                                         ("down", (H, F_), aq, as_, dns, "bf16" if shard else "slabs")):
                     fns = {}
                     for ntf in (2, 4):
                         for S in ((1, 2, 4, 7, 8, 14, 16) if epi == "slabs" else (1,)):
-                            if K_ % (128 * S) or N_ % (16 * ntf) or (N_ // (16 * ntf)) * S > 4096:
+                            if K_ % (chunk * S) or N_ % (16 * ntf) or (N_ // (16 * ntf)) * S > 4096:
                                 continue
-                            wq = [(w.gate_up_q, w.gate_up_s) if name == "gate_up" else (w.down_q, w.down_s) for w in q]
-                            fns[f"S{S}_ntf{ntf}"] = (lambda S=S, ntf=ntf, wq=wq, x_=x_, s_=s_, epi=epi:
-                                                     fp8_dense.dense_fp8_gemm(x_, s_, *wq[nxt(copies)], epi, S, ntf))
-                    t = _timeit_interleaved(fns, iters=2 * copies, rounds=5)
+                            fns[f"S{S}_ntf{ntf}"] = (lambda S=S, ntf=ntf, ws_=ws_, x_=x_, s_=s_, epi=epi:
+                                                     dense_gemm(x_, s_, *ws_[nxt(wcopies)], epi, S, ntf))
+                    t = _timeit_interleaved(fns, iters=2 * wcopies, rounds=5)
                     best = min(t, key=t.get)
-                    row = {"bench": "dense_fp8_sweep", "model": model, "M": M, name: {"shape": [N_, K_]}, "epi": epi,
+                    row = {"bench": f"dense_{fmt}_sweep", "model": model, "M": M, name: {"shape": [N_, K_]}, "epi": epi,
                            "us": {k: round(v, 1) for k, v in t.items()}, "best": best,
-                           "best_TBps": round(N_ * K_ / t[best] / 1e6, 2)}
+                           "best_TBps": round(wbytes(N_, K_) / t[best] / 1e6, 2)}
                     out.append(row)
                     print(json.dumps(row), flush=True)
                 continue
-            w0 = q[0]
-            path = fp8_dense.mlp_fp8_path(h, w0)
-            fns = {"fp8": lambda: fp8_dense.mlp_fp8(h, q[nxt(copies)], slabs=not shard), "bf16": lambda: bf16_mlp(h)}
-            t = _timeit_interleaved(fns, iters=2 * max(copies, bcopies))
-            row = {"bench": "dense_fp8_mlp", "model": model, "M": M, "path": path, "fp8_us": round(t["fp8"], 1),
-                   "bf16_us": round(t["bf16"], 1), "speedup": round(t["bf16"] / t["fp8"], 2),
-                   "winner": "fp8" if t["fp8"] < t["bf16"] else "bf16"}
-            # the fp8 path's stages alone
-            xq, xs = fp8_dense._quant(h)
-            _, a = fp8_dense.mlp_fp8(h, w0)
-            aq, as_ = fp8_dense._quant(a)
-            st = N.stream
-            if path == "stream":
-                _, ntf1 = fp8_dense.dense_fp8_config(M, 2 * F_, H, "silu")
-                epi2 = "bf16" if shard else "slabs"
-                S2, ntf2 = fp8_dense.dense_fp8_config(M, H, F_, epi2)
-                parts = {"gate_up": lambda: fp8_dense.dense_fp8_gemm(xq, xs, q[nxt(copies)].gate_up_q, q[it[0] % copies].gate_up_s,
-                                                                     "silu", 1, ntf1),
-                         "down": lambda: fp8_dense.dense_fp8_gemm(aq, as_, q[nxt(copies)].down_q, q[it[0] % copies].down_s,
-                                                                  epi2, S2, ntf2)}
-                cfgs = {"gate_up": [1, ntf1], "down": [S2, ntf2]}
+            path = mlp_path(h, wq[0])
+            fns = {fmt: lambda: mlp(h, wq[nxt(wcopies)], slabs=not shard)}
+            if m4:
+                fns["fp8"] = lambda: fp8_dense.mlp_fp8(h, q[nxt(copies)], slabs=not shard)
+            fns["bf16"] = lambda: bf16_mlp(h)
+            t = _timeit_interleaved(fns, iters=2 * ncopy)
+            row = {"bench": f"dense_{fmt}_mlp", "model": model, "M": M, "path": path}
+            if m4:
+                row.update(mxfp4_us=round(t["mxfp4"], 1), fp8_us=round(t["fp8"], 1), bf16_us=round(t["bf16"], 1),
+                           speedup_vs_bf16=round(t["bf16"] / t["mxfp4"], 2), speedup_vs_fp8=round(t["fp8"] / t["mxfp4"], 2),
+                           winner=min(t, key=t.get))
             else:
+                row.update(fp8_us=round(t["fp8"], 1), bf16_us=round(t["bf16"], 1), speedup=round(t["bf16"] / t["fp8"], 2),
+                           winner="fp8" if t["fp8"] < t["bf16"] else "bf16")
+            # ``fmt``'s stages alone
+            _, a = mlp(h, wq[0])
+            aq, as_ = fp8_dense._quant(a)
+            parts = {}
+            if path == "stream":
+                _, ntf1 = config(M, 2 * F_, H, "silu")
+                epi2 = "bf16" if shard else "slabs"
+                S2, ntf2 = config(M, H, F_, epi2)
+                parts["gate_up"] = lambda: dense_gemm(xq, xs, *gus[nxt(wcopies)], "silu", 1, ntf1)
+                parts["down"] = lambda: dense_gemm(aq, as_, *dns[nxt(wcopies)], epi2, S2, ntf2)
+                cfgs = {"gate_up": [1, ntf1], "down": [S2, ntf2]}
+            elif m4:
+                def ex():
+                    w = wq[nxt(wcopies)]
+                    mxfp4_dense.expand_mxfp4(w.gate_up_c, w.gate_up_e, out=scratch.gate_up)
+                    mxfp4_dense.expand_mxfp4(w.down_c, w.down_e, out=scratch.down)
+                parts["expand"] = ex
+                cfgs = {"gate_up": "expand + fp8", "down": "expand + fp8"}
+            else:
+                st = N.stream
                 off, ones = fp8_dense._bucket(dev, M)
                 ab = torch.empty((M, F_), dtype=torch.bfloat16, device=dev)
                 yb = torch.empty((M, H), dtype=torch.bfloat16, device=dev)
@@ -2337,137 +2367,11 @@ def bench_dense_fp8_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128
                     w = q[nxt(copies)]
                     N.call("penny_moe_gemm_prefill_fp8", N.ptr(aq), F_, None, N.ptr(as_), N.ptr(off), N.ptr(w.down_q),
                            N.ptr(w.down_s), N.ptr(ones), N.ptr(yb), H, M, 1, H, F_, 8, st())
-                parts = {"gate_up": g1, "down": g2}
+                parts.update(gate_up=g1, down=g2)
                 cfgs = {"gate_up": "tile", "down": "tile"}
             parts["quant_h"] = lambda: fp8_dense._quant(h)
             parts["quant_a"] = lambda: fp8_dense._quant(a)
-            pt = _timeit_interleaved(parts, iters=2 * copies, rounds=5)
-            for name, (N_, K_) in (("gate_up", (2 * F_, H)), ("down", (H, F_))):
-                row[name] = {"shape": [N_, K_], "cfg": cfgs[name], "us": round(pt[name], 1),
-                             "W_TBps": round(N_ * K_ / pt[name] / 1e6, 2)}
-            row["quant_us"] = [round(pt["quant_h"], 1), round(pt["quant_a"], 1)]
-            out.append(row)
-            print(json.dumps(row), flush=True)
-        del q, bw
-        torch.cuda.empty_cache()
-    return out
-
-
-def bench_dense_mxfp4_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 128, 256, 512, 2048),
-                          sweep: bool = False) -> List[Dict]:
-    """One dense Llama MLP with MXFP4 weights (``ops.mlp_mxfp4``: the 4-bit streaming kernel up to 256 rows,
-    the e4m3 expansion + the fp8 kernels above; the row-quantisation passes and the expansion included)
-    against fp8 (``ops.mlp_fp8``) and bf16 (``linear`` as ``DecoderModel.mlp`` calls it), the three taking
-    turns in one process, each format's weights rotated over copies so every call streams W from HBM.
-    Reports the three times, the winner, and for the mxfp4 path each stage alone with the TB/s of the W bytes
-    it reads (codes + exponents).  ``sweep``: instead, every (S, ntf) candidate of the 4-bit kernel per GEMM
-    and M <= 256 (the numbers ``ops.mxfp4_dense.DENSE_MXFP4`` is chosen from)."""
-    from ..ops import fp8_dense, gemm, mxfp4_dense
-    out = []
-    g = torch.Generator(device=dev).manual_seed(0)
-    for model in models:
-        H, F_, tuning = DENSE_FP8_MODELS[model]
-        shard = model.endswith("tp8")
-        if tuning:
-            gemm.load_gemm_tuning(tuning)
-        copies = max(2, -(-(768 << 20) // (3 * H * F_)))
-        bcopies = max(2, -(-(768 << 20) // (6 * H * F_)))
-        mcopies = max(2, -(-(768 << 20) // (3 * H * F_ // 2)))
-        q, bw, m4 = [], [], []
-        scratch = mxfp4_dense.ExpandScratch(H, F_, dev)
-        for c in range(max(copies, bcopies, mcopies)):
-            gu = (torch.randn((2 * F_, H), device=dev, generator=g) * 0.02).to(torch.bfloat16)
-            dn = (torch.randn((H, F_), device=dev, generator=g) * 0.02).to(torch.bfloat16)
-            m4.append(mxfp4_dense.quantize_dense_mlp_mxfp4(gu, dn, scratch=scratch))
-            if c < copies and not sweep:
-                q.append(fp8_dense.quantize_dense_mlp(gu, dn))
-            if c < bcopies and not sweep:
-                ent = {"gu": gu, "dn": dn, "gut": None, "dnt": None}
-                if gemm.uses_tiled_weight(2 * F_, H):
-                    ent["gut"] = gemm.tile_weight(gu)
-                    if gemm.tiled_only(2 * F_, H):
-                        ent["gu"] = None
-                if gemm.uses_tiled_weight(H, F_):
-                    ent["dnt"] = gemm.tile_weight(dn)
-                bw.append(ent)
-            del gu, dn
-        mcopies = len(m4)
-        it = [0]
-
-        def nxt(n):
-            it[0] += 1
-            return it[0] % n
-
-        def bf16_mlp(h):
-            e = bw[nxt(bcopies)]
-            if e["gu"] is None:
-                a = gemm.linear_tiled(h, e["gut"], 2 * F_, epilogue="silu")
-            else:
-                a = gemm.linear(h, e["gu"], epilogue="silu", wt=e["gut"])
-            return gemm.linear(a, e["dn"], wt=e["dnt"], slabs=not shard)
-
-        wbytes = lambda N_, K_: N_ * K_ // 2 + N_ * K_ // 32      # noqa: E731
-        for M in Ms:
-            h = torch.randn((M, H), device=dev, generator=g).to(torch.bfloat16)
-            xq, xs = fp8_dense._quant(h)
-            if sweep:
-                if M > mxfp4_dense.MAX_M:
-                    continue
-                a = torch.randn((M, F_), device=dev, generator=g).to(torch.bfloat16)
-                aq, as_ = fp8_dense._quant(a)
-                for name, (N_, K_), x_, s_, epi in (("gate_up", (2 * F_, H), xq, xs, "silu"),
-                                                    ("down", (H, F_), aq, as_, "bf16" if shard else "slabs")):
-                    fns = {}
-                    for ntf in (2, 4):
-                        for S in ((1, 2, 4, 7, 8, 14, 16) if epi == "slabs" else (1,)):
-                            if K_ % (256 * S) or N_ % (16 * ntf) or (N_ // (16 * ntf)) * S > 4096:
-                                continue
-                            ws_ = [(w.gate_up_c, w.gate_up_e, w.gate_up_s) if name == "gate_up" else
-                                   (w.down_c, w.down_e, w.down_s) for w in m4]
-                            fns[f"S{S}_ntf{ntf}"] = (lambda S=S, ntf=ntf, ws_=ws_, x_=x_, s_=s_, epi=epi:
-                                                     mxfp4_dense.dense_mxfp4_gemm(x_, s_, *ws_[nxt(mcopies)], epi, S, ntf))
-                    t = _timeit_interleaved(fns, iters=2 * mcopies, rounds=5)
-                    best = min(t, key=t.get)
-                    row = {"bench": "dense_mxfp4_sweep", "model": model, "M": M, name: {"shape": [N_, K_]}, "epi": epi,
-                           "us": {k: round(v, 1) for k, v in t.items()}, "best": best,
-                           "best_TBps": round(wbytes(N_, K_) / t[best] / 1e6, 2)}
-                    out.append(row)
-                    print(json.dumps(row), flush=True)
-                continue
-            path = mxfp4_dense.mlp_mxfp4_path(h, m4[0])
-            fns = {"mxfp4": lambda: mxfp4_dense.mlp_mxfp4(h, m4[nxt(mcopies)], slabs=not shard),
-                   "fp8": lambda: fp8_dense.mlp_fp8(h, q[nxt(copies)], slabs=not shard), "bf16": lambda: bf16_mlp(h)}
-            t = _timeit_interleaved(fns, iters=2 * max(copies, bcopies, mcopies))
-            row = {"bench": "dense_mxfp4_mlp", "model": model, "M": M, "path": path, "mxfp4_us": round(t["mxfp4"], 1),
-                   "fp8_us": round(t["fp8"], 1), "bf16_us": round(t["bf16"], 1),
-                   "speedup_vs_bf16": round(t["bf16"] / t["mxfp4"], 2), "speedup_vs_fp8": round(t["fp8"] / t["mxfp4"], 2),
-                   "winner": min(t, key=t.get)}
-            # the mxfp4 path's stages alone
-            _, a = mxfp4_dense.mlp_mxfp4(h, m4[0])
-            aq, as_ = fp8_dense._quant(a)
-            parts = {"quant_h": lambda: fp8_dense._quant(h), "quant_a": lambda: fp8_dense._quant(a)}
-            if path == "stream":
-                _, ntf1 = mxfp4_dense.dense_mxfp4_config(M, 2 * F_, H, "silu")
-                epi2 = "bf16" if shard else "slabs"
-                S2, ntf2 = mxfp4_dense.dense_mxfp4_config(M, H, F_, epi2)
-
-                def g1():
-                    w = m4[nxt(mcopies)]
-                    mxfp4_dense.dense_mxfp4_gemm(xq, xs, w.gate_up_c, w.gate_up_e, w.gate_up_s, "silu", 1, ntf1)
-
-                def g2():
-                    w = m4[nxt(mcopies)]
-                    mxfp4_dense.dense_mxfp4_gemm(aq, as_, w.down_c, w.down_e, w.down_s, epi2, S2, ntf2)
-                parts.update(gate_up=g1, down=g2)
-                cfgs = {"gate_up": [1, ntf1], "down": [S2, ntf2]}
-            else:
-                def ex():
-                    w = m4[nxt(mcopies)]
-                    mxfp4_dense.expand_mxfp4(w.gate_up_c, w.gate_up_e, out=scratch.gate_up)
-                    mxfp4_dense.expand_mxfp4(w.down_c, w.down_e, out=scratch.down)
-                parts["expand"] = ex
-                cfgs = {"gate_up": "expand + fp8", "down": "expand + fp8"}
-            pt = _timeit_interleaved(parts, iters=2 * mcopies, rounds=5)
+            pt = _timeit_interleaved(parts, iters=2 * wcopies, rounds=5)
             for name, (N_, K_) in (("gate_up", (2 * F_, H)), ("down", (H, F_))):
                 row[name] = {"shape": [N_, K_], "cfg": cfgs[name]}
                 if name in pt:
@@ -2479,7 +2383,7 @@ def bench_dense_mxfp4_mlp(dev, models=("8b", "70b", "70b_tp8"), Ms=(1, 16, 64, 1
                 row["expand_TBps"] = round((wbytes(3 * F_, H) + 3 * F_ * H) / pt["expand"] / 1e6, 2)
             out.append(row)
             print(json.dumps(row), flush=True)
-        del q, bw, m4, scratch
+        del q, bw, w4, wq, gus, dns, scratch
         torch.cuda.empty_cache()
     return out
 
@@ -2527,10 +2431,10 @@ def main(argv=None) -> int:
                 "topn_logprob": bench_topn_logprob,
                 "lora": bench_lora,
                 "kv_tier": bench_kv_tier,
-                "dense_fp8_mlp": bench_dense_fp8_mlp,
-                "dense_fp8_sweep": lambda d: bench_dense_fp8_mlp(d, Ms=(1, 16, 64, 128, 256), sweep=True),
-                "dense_mxfp4_mlp": bench_dense_mxfp4_mlp,
-                "dense_mxfp4_sweep": lambda d: bench_dense_mxfp4_mlp(d, Ms=(1, 16, 64, 128, 256), sweep=True),
+                "dense_fp8_mlp": lambda d: bench_dense_mlp(d, "fp8"),
+                "dense_fp8_sweep": lambda d: bench_dense_mlp(d, "fp8", Ms=(1, 16, 64, 128, 256), sweep=True),
+                "dense_mxfp4_mlp": lambda d: bench_dense_mlp(d, "mxfp4"),
+                "dense_mxfp4_sweep": lambda d: bench_dense_mlp(d, "mxfp4", Ms=(1, 16, 64, 128, 256), sweep=True),
                 "lm_head_sample_logprob_sweep": lambda d: bench_lm_head_sample_logprob(
                     d, Ms=(1, 8, 16, 32, 48, 64, 96, 127, 128, 160, 192, 256)),
                 "lm_head_stream": bench_lm_head_stream, "decode_8b": lambda d: bench_shard_shapes(d, names=("8b_qkv", "8b_o", "8b_down"), Ms=(32, 64, 96, 128, 160, 192, 256), prefill_Ms=()), "gateup_shapes": lambda d: bench_shard_shapes(d, names=("70b_tp8_gate_up", "70b_tp1_gate_up", "8b_gate_up"), prefill_Ms=()),

@@ -238,8 +238,6 @@ class DecoderModel:
             self.wt.pop(p + "down", None)
             if dtype == "fp8":
                 q = ops.quantize_dense_mlp(gu, down)
-                self.w[p + "gate_up_q"], self.w[p + "gate_up_scale"] = q.gate_up_q, q.gate_up_s
-                self.w[p + "down_q"], self.w[p + "down_scale"] = q.down_q, q.down_s
             else:
                 if scratch is None and self.device.type == "cuda":
                     # one layer's e4m3 MLP for steps above 256 rows, allocated now: the KV pool is sized after it
@@ -251,8 +249,8 @@ class DecoderModel:
                 if self.tp_size > 1 and comm.tp_size() == self.tp_size:
                     amax = comm.tp_all_reduce_max(down.float().abs().amax(dim=1))
                 q = ops.quantize_dense_mlp_mxfp4(gu, down, scratch=scratch, down_row_amax=amax)
-                self.w[p + "gate_up_c"], self.w[p + "gate_up_e"], self.w[p + "gate_up_scale"] = q.gate_up_c, q.gate_up_e, q.gate_up_s
-                self.w[p + "down_c"], self.w[p + "down_e"], self.w[p + "down_scale"] = q.down_c, q.down_e, q.down_s
+            for key, t in q.named_tensors().items():
+                self.w[p + key] = t
             del gu, down
             self.mlp_q[i] = q
         self.mlp_dtype = dtype
@@ -284,16 +282,11 @@ class DecoderModel:
             fuse_residual: Optional[torch.Tensor] = None, row_slot: Optional[torch.Tensor] = None,
             lora=None) -> torch.Tensor:
         p = f"layers.{i}."
-        if self.mlp_dtype == "fp8":
-            # W8A8 (ops.fp8_dense): decode sizes return split-K slabs at TP=1 like the bf16 down GEMM;
-            # no residual epilogue (the consumer's add + RMSNorm adds it)
-            out, a = ops.mlp_fp8(h, self.mlp_q[i], slabs=self.tp_size == 1)
-            if row_slot is not None:
-                out = self._lora_delta(out, a, i, "down", row_slot, lora)
-            return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out
-        if self.mlp_dtype == "mxfp4":
-            # W4A8 (ops.mxfp4_dense): the fp8 branch's outputs and consumers
-            out, a = ops.mlp_mxfp4(h, self.mlp_q[i], slabs=self.tp_size == 1)
+        if self.mlp_dtype != "bf16":
+            # W8A8 (ops.fp8_dense) or W4A8 (ops.mxfp4_dense): decode sizes return split-K slabs at TP=1 like
+            # the bf16 down GEMM; no residual epilogue (the consumer's add + RMSNorm adds it)
+            run = ops.mlp_fp8 if self.mlp_dtype == "fp8" else ops.mlp_mxfp4
+            out, a = run(h, self.mlp_q[i], slabs=self.tp_size == 1)
             if row_slot is not None:
                 out = self._lora_delta(out, a, i, "down", row_slot, lora)
             return comm.tp_all_reduce(out) if self.tp_size > 1 and reduce else out

@@ -11,14 +11,18 @@ One fp8 contract with the Mixtral experts (``ops/moe.py``):
   split-K :class:`~.gemm.Slabs` for ``ops.rms_norm``.
 
 ``mlp_fp8`` takes, on the GPU: up to 256 rows the weight-streaming kernel of
-``csrc/kernels/gemm_fp8_dense.hip`` (``penny_dense_fp8_gemm``), above that the grouped fp8 tile GEMM
+``csrc/kernels/gemm_dense_stream.hip`` (``penny_dense_fp8_gemm``), above that the grouped fp8 tile GEMM
 of ``gemm_prefill.hip`` with a single bucket; shapes outside both kernels' contracts, and CPU
 tensors, take the torch path (same operation order).  One copy of each weight: both kernels read
 the row-major ``[N, K]`` codes.
+
+The streaming kernel has a second weight format (``ops/mxfp4_dense.py``); what the two share on the host
+is written here once and takes the format's table, chunk width and functions: ``_config``,
+``_default_config``, ``_alloc_out``, ``_stream_ok`` and ``_mlp_stream``.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
@@ -30,6 +34,8 @@ from .moe import _fake_quant_rows, moe_fp8_reference, quantize_fp8_rowwise, TILE
 EPI = {"silu": 1, "bf16": 2, "slabs": 3}
 MAX_M = 256            # the streaming kernel's row range (ops.gemm.linear's decode-size steps)
 MAX_S = 16             # K slices the kernel supports (slabs only)
+CHUNK = 128            # columns of one wave step: two pairs of 16x16x32 MFMAs
+Table = Dict[Tuple[int, int], List[Tuple[int, int, int]]]
 
 
 class DenseFp8MLP:
@@ -49,8 +55,12 @@ class DenseFp8MLP:
     def F(self) -> int:
         return self.down_q.shape[1]
 
+    def named_tensors(self) -> Dict[str, torch.Tensor]:
+        """Weight-dict key suffix -> tensor, in the constructor's order."""
+        return {"gate_up_q": self.gate_up_q, "gate_up_scale": self.gate_up_s, "down_q": self.down_q, "down_scale": self.down_s}
+
     def tensors(self) -> Tuple[torch.Tensor, ...]:
-        return (self.gate_up_q, self.gate_up_s, self.down_q, self.down_s)
+        return tuple(self.named_tensors().values())
 
     def num_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors())
@@ -74,7 +84,7 @@ def quantize_dense_mlp(gate_up: torch.Tensor, down: torch.Tensor) -> DenseFp8MLP
 # halve the activation bytes a workgroup pulls from L2 per weight byte and win wherever the grid still
 # covers the CUs (8B gate|up at 128 rows: 63 vs 85 us); the narrow TP=8 shards keep 32-row groups.
 # Shapes without an entry take ``_default_config``.
-DENSE_FP8: Dict[Tuple[int, int], List[Tuple[int, int, int]]] = {
+DENSE_FP8: Table = {
     # Llama-3-8B (profiles/dense_fp8_sweep.jsonl)
     (28672, 4096): [(256, 1, 4)],                    # gate|up: 448 workgroups; 28.5 us at 1 row, 63 at 128
     (4096, 14336): [(16, 8, 4), (256, 4, 4)],        # down: 64 x 8 to 16 rows (12.9-14.3 us), 64 x 4 above
@@ -87,36 +97,49 @@ DENSE_FP8: Dict[Tuple[int, int], List[Tuple[int, int, int]]] = {
 }
 
 
-def _default_config(N_: int, K: int) -> Optional[Tuple[int, int]]:
+def _default_config(N_: int, K: int, chunk: int = CHUNK) -> Optional[Tuple[int, int]]:
     """(S, ntf) for an unmeasured shape: 32-row groups, K slices until the grid covers the 256 CUs."""
-    if N_ % 32 or K % 128:
+    if N_ % 32 or K % chunk:
         return None
     S = 1
-    while S < 8 and (N_ // 32) * S < 256 and K % (256 * S) == 0:
+    while S < 8 and (N_ // 32) * S < 256 and K % (2 * chunk * S) == 0:
         S *= 2
     return S, 2
 
 
-def dense_fp8_config(M: int, N_: int, K: int, epilogue: str) -> Optional[Tuple[int, int]]:
-    """(S, ntf) for the streaming kernel at this shape and epilogue, or None where its contract
-    (1 <= M <= 256, K % (128 S) == 0, N % (16 ntf) == 0) does not hold."""
-    if not 1 <= M <= MAX_M or K % 128:
+def _config(table: Table, chunk: int, M: int, N_: int, K: int, epilogue: str) -> Optional[Tuple[int, int]]:
+    """(S, ntf) of a streaming kernel with ``chunk``-column wave steps from its ``table``, or None where its
+    contract (1 <= M <= 256, K % (chunk S) == 0, N % (16 ntf) == 0) does not hold."""
+    if not 1 <= M <= MAX_M or K % chunk:
         return None
     cfg = None
-    for max_m, S, ntf in DENSE_FP8.get((N_, K), ()):
+    for max_m, S, ntf in table.get((N_, K), ()):
         if M <= max_m:
             cfg = (S, ntf)
             break
     if cfg is None:
-        cfg = _default_config(N_, K)
+        cfg = _default_config(N_, K, chunk)
     if cfg is None:
         return None
     S, ntf = cfg
     if epilogue != "slabs":
         S = 1
-    if N_ % (16 * ntf) or K % (128 * S) or not 1 <= S <= MAX_S:
+    if N_ % (16 * ntf) or K % (chunk * S) or not 1 <= S <= MAX_S:
         return None
     return S, ntf
+
+
+def dense_fp8_config(M: int, N_: int, K: int, epilogue: str) -> Optional[Tuple[int, int]]:
+    """(S, ntf) for the streaming kernel at this shape and epilogue, or None where its contract
+    (1 <= M <= 256, K % (128 S) == 0, N % (16 ntf) == 0) does not hold."""
+    return _config(DENSE_FP8, CHUNK, M, N_, K, epilogue)
+
+
+def _alloc_out(xq: torch.Tensor, M: int, N_: int, epilogue: str, S: int) -> torch.Tensor:
+    """The output of one streaming GEMM: "slabs" f32 [S, M, N]; "silu" bf16 [M, N/2]; "bf16" [M, N]."""
+    if epilogue == "slabs":
+        return torch.empty((S, M, N_), dtype=torch.float32, device=xq.device)
+    return torch.empty((M, N_ // 2 if epilogue == "silu" else N_), dtype=torch.bfloat16, device=xq.device)
 
 
 def dense_fp8_gemm(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, epilogue: str,
@@ -132,13 +155,9 @@ def dense_fp8_gemm(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: tor
     if wq.shape[1] != K or not wq.is_contiguous() or xq.stride(1) != 1:
         raise ValueError("dense_fp8_gemm: wq must be contiguous [N, K], xq rows contiguous")
     if out is None:
-        if epilogue == "slabs":
-            out = torch.empty((S, M, N_), dtype=torch.float32, device=xq.device)
-        else:
-            out = torch.empty((M, N_ // 2 if epilogue == "silu" else N_), dtype=torch.bfloat16, device=xq.device)
-    ldy = out.stride(-2)
-    N.call("penny_dense_fp8_gemm", N.ptr(xq), xq.stride(0), N.ptr(xs), N.ptr(wq), N.ptr(ws), N.ptr(out), ldy,
-           M, N_, K, EPI[epilogue], S, ntf, N.stream())
+        out = _alloc_out(xq, M, N_, epilogue, S)
+    N.call("penny_dense_fp8_gemm", N.ptr(xq), xq.stride(0), N.ptr(xs), N.ptr(wq), N.ptr(ws), N.ptr(out),
+           out.stride(-2), M, N_, K, EPI[epilogue], S, ntf, N.stream())
     return out
 
 
@@ -165,9 +184,27 @@ def _bucket(dev: torch.device, M: int) -> Tuple[torch.Tensor, torch.Tensor]:
     return off, ones
 
 
-def _stream_ok(M: int, w: DenseFp8MLP) -> bool:
+def _stream_ok(M: int, w, config: Callable = dense_fp8_config) -> bool:
+    """Both GEMMs of ``w`` (anything with ``H`` and ``F``) are in the contract of ``config``'s streaming kernel."""
     H, F_ = w.H, w.F
-    return dense_fp8_config(M, 2 * F_, H, "silu") is not None and dense_fp8_config(M, H, F_, "slabs") is not None
+    return config(M, 2 * F_, H, "silu") is not None and config(M, H, F_, "slabs") is not None
+
+
+def _mlp_stream(h: torch.Tensor, slabs: bool, config: Callable, gemm: Callable, gate_up: Tuple[torch.Tensor, ...],
+                down: Tuple[torch.Tensor, ...]) -> Tuple[Union[torch.Tensor, Slabs], torch.Tensor]:
+    """The streaming MLP of either format: quantise, gate|up SiLU GEMM, quantise, down GEMM as slabs or
+    bf16.  ``config`` / ``gemm``: the format's ``dense_*_config`` / ``dense_*_gemm``; ``gate_up`` / ``down``:
+    the weight tensors ``gemm`` takes after ``xq, xs``."""
+    M, H = h.shape
+    F_ = gate_up[0].shape[0] // 2
+    xq, xs = _quant(h)
+    _, ntf = config(M, 2 * F_, H, "silu")
+    a = gemm(xq, xs, *gate_up, "silu", 1, ntf)
+    aq, as_ = _quant(a)
+    S, ntf = config(M, H, F_, "slabs" if slabs else "bf16")
+    if slabs:
+        return Slabs(gemm(aq, as_, *down, "slabs", S, ntf)), a
+    return gemm(aq, as_, *down, "bf16", 1, ntf), a
 
 
 def _tiles_ok(M: int, w: DenseFp8MLP) -> bool:
@@ -197,15 +234,9 @@ def mlp_fp8(h: torch.Tensor, w: DenseFp8MLP, slabs: bool = False) -> Tuple[Union
         return _mlp_torch(h, w)
     if h.stride(1) != 1 or h.stride(0) % 8:
         h = h.contiguous()
-    xq, xs = _quant(h)
     if path == "stream":
-        _, ntf = dense_fp8_config(M, 2 * F_, H, "silu")
-        a = dense_fp8_gemm(xq, xs, w.gate_up_q, w.gate_up_s, "silu", 1, ntf)
-        aq, as_ = _quant(a)
-        S, ntf = dense_fp8_config(M, H, F_, "slabs" if slabs else "bf16")
-        if slabs:
-            return Slabs(dense_fp8_gemm(aq, as_, w.down_q, w.down_s, "slabs", S, ntf)), a
-        return dense_fp8_gemm(aq, as_, w.down_q, w.down_s, "bf16", 1, ntf), a
+        return _mlp_stream(h, slabs, dense_fp8_config, dense_fp8_gemm, (w.gate_up_q, w.gate_up_s), (w.down_q, w.down_s))
+    xq, xs = _quant(h)
     # prefill sizes: the grouped fp8 tile GEMM with one bucket [0, M) (epi 7: SiLU; epi 8: x route_w = 1)
     dev = h.device
     st = N.stream()

@@ -18,24 +18,22 @@ to bf16 once before ``silu_mul(interleave16=True)``, down rounded to bf16 once o
 f32 :class:`~.gemm.Slabs`.
 
 ``mlp_mxfp4`` takes, on the GPU: "stream" -- up to 256 rows, ``penny_dense_mxfp4_gemm``
-(``csrc/kernels/gemm_mxfp4_dense.hip``) reads the codes; "expand" -- above that (or where K is a
+(``csrc/kernels/gemm_dense_stream.hip``) reads the codes; "expand" -- above that (or where K is a
 multiple of 128 and not of 256), each projection is expanded into a persistent e4m3 scratch
 (``penny_mxfp4_expand``) and ``mlp_fp8`` runs on a :class:`~.fp8_dense.DenseFp8MLP` view of it;
 "torch" -- CPU tensors and whatever neither accepts, in the kernels' operation order.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 
 from . import _native as N
 from . import fp8_dense
-from .fp8_dense import DenseFp8MLP, EPI, _quant, dense_fp8_reference, mlp_fp8
+from .fp8_dense import DenseFp8MLP, EPI, MAX_M, MAX_S, _quant, dense_fp8_reference, mlp_fp8
 from .gemm import Slabs
 
-MAX_M = 256            # the streaming kernel's row range
-MAX_S = 16             # K slices the kernel supports (slabs only)
 CHUNK = 256            # columns of one wave step: two 16x16x128 MFMAs
 E_MIN, E_MAX = -8, 0   # block exponents the format holds (every e2m1 * 2^e an e4m3 value)
 E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
@@ -71,8 +69,13 @@ class DenseMxfp4MLP:
     def F(self) -> int:
         return self.down_c.shape[1] * 2
 
+    def named_tensors(self) -> Dict[str, torch.Tensor]:
+        """Weight-dict key suffix -> tensor, in the constructor's order."""
+        return {"gate_up_c": self.gate_up_c, "gate_up_e": self.gate_up_e, "gate_up_scale": self.gate_up_s,
+                "down_c": self.down_c, "down_e": self.down_e, "down_scale": self.down_s}
+
     def tensors(self) -> Tuple[torch.Tensor, ...]:
-        return (self.gate_up_c, self.gate_up_e, self.gate_up_s, self.down_c, self.down_e, self.down_s)
+        return tuple(self.named_tensors().values())
 
     def num_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors())
@@ -212,7 +215,7 @@ def expand_mxfp4(codes: torch.Tensor, exps: torch.Tensor, out: Optional[torch.Te
 # (1-16, 64-256) the candidate with the smallest summed time relative to each row count's best; the chosen configs
 # against bf16 and fp8: --only dense_mxfp4_mlp (profiles/dense_mxfp4_mlp.jsonl).  Shapes without an entry take
 # ``_default_config``.
-DENSE_MXFP4: Dict[Tuple[int, int], List[Tuple[int, int, int]]] = {
+DENSE_MXFP4: fp8_dense.Table = {
     # Llama-3-8B
     (28672, 4096): [(256, 1, 4)],                    # gate|up: 448 workgroups
     (4096, 14336): [(16, 2, 2), (256, 4, 4)],        # down: 128 x 2 to 16 rows, 64 x 4 above
@@ -227,34 +230,15 @@ DENSE_MXFP4: Dict[Tuple[int, int], List[Tuple[int, int, int]]] = {
 
 def _default_config(N_: int, K: int) -> Optional[Tuple[int, int]]:
     """(S, ntf) for an unmeasured shape: 32-row groups, K slices until the grid covers the 256 CUs."""
-    if N_ % 32 or K % CHUNK:
-        return None
-    S = 1
-    while S < 8 and (N_ // 32) * S < 256 and K % (2 * CHUNK * S) == 0:
-        S *= 2
-    return S, 2
+    return fp8_dense._default_config(N_, K, CHUNK)
 
 
 def dense_mxfp4_config(M: int, N_: int, K: int, epilogue: str) -> Optional[Tuple[int, int]]:
     """(S, ntf) for the streaming kernel at this shape and epilogue, or None where its contract
     (1 <= M <= 256, K % (256 S) == 0, N % (16 ntf) == 0) does not hold."""
-    if not 1 <= M <= MAX_M or K % CHUNK or K <= 0:
+    if K <= 0:
         return None
-    cfg = None
-    for max_m, S, ntf in DENSE_MXFP4.get((N_, K), ()):
-        if M <= max_m:
-            cfg = (S, ntf)
-            break
-    if cfg is None:
-        cfg = _default_config(N_, K)
-    if cfg is None:
-        return None
-    S, ntf = cfg
-    if epilogue != "slabs":
-        S = 1
-    if N_ % (16 * ntf) or K % (CHUNK * S) or not 1 <= S <= MAX_S:
-        return None
-    return S, ntf
+    return fp8_dense._config(DENSE_MXFP4, CHUNK, M, N_, K, epilogue)
 
 
 def dense_mxfp4_gemm(xq: torch.Tensor, xs: torch.Tensor, wc: torch.Tensor, we: torch.Tensor, ws: torch.Tensor,
@@ -271,13 +255,9 @@ def dense_mxfp4_gemm(xq: torch.Tensor, xs: torch.Tensor, wc: torch.Tensor, we: t
             or xq.stride(1) != 1):
         raise ValueError("dense_mxfp4_gemm: wc [N, K/2] and we [N, K/32] contiguous, xq rows contiguous")
     if out is None:
-        if epilogue == "slabs":
-            out = torch.empty((S, M, N_), dtype=torch.float32, device=xq.device)
-        else:
-            out = torch.empty((M, N_ // 2 if epilogue == "silu" else N_), dtype=torch.bfloat16, device=xq.device)
-    ldy = out.stride(-2)
+        out = fp8_dense._alloc_out(xq, M, N_, epilogue, S)
     N.call("penny_dense_mxfp4_gemm", N.ptr(xq), xq.stride(0), N.ptr(xs), N.ptr(wc), N.ptr(we), N.ptr(ws), N.ptr(out),
-           ldy, M, N_, K, EPI[epilogue], S, ntf, N.stream())
+           out.stride(-2), M, N_, K, EPI[epilogue], S, ntf, N.stream())
     return out
 
 
@@ -285,8 +265,7 @@ def dense_mxfp4_gemm(xq: torch.Tensor, xs: torch.Tensor, wc: torch.Tensor, we: t
 # the MLP
 # ---------------------------------------------------------------------------------------------
 def _stream_ok(M: int, w: DenseMxfp4MLP) -> bool:
-    H, F_ = w.H, w.F
-    return dense_mxfp4_config(M, 2 * F_, H, "silu") is not None and dense_mxfp4_config(M, H, F_, "slabs") is not None
+    return fp8_dense._stream_ok(M, w, dense_mxfp4_config)
 
 
 def _expanded(w: DenseMxfp4MLP, fill: bool) -> DenseFp8MLP:
@@ -315,8 +294,6 @@ def mlp_mxfp4(h: torch.Tensor, w: DenseMxfp4MLP, slabs: bool = False) -> Tuple[U
     """The MXFP4 MLP of ``h`` [M, H] bf16 -> (down output, bf16 intermediate ``a`` [M, F]), as
     :func:`~.fp8_dense.mlp_fp8`: bf16 [M, H], or with ``slabs`` at decode sizes the unreduced f32
     :class:`~.gemm.Slabs` of the down GEMM."""
-    M, H = h.shape
-    F_ = w.F
     path = mlp_mxfp4_path(h, w)
     if path == "torch":
         return _mlp_torch(h, w)
@@ -326,14 +303,8 @@ def mlp_mxfp4(h: torch.Tensor, w: DenseMxfp4MLP, slabs: bool = False) -> Tuple[U
         return mlp_fp8(h, _expanded(w, fill=True), slabs=slabs)
     if h.stride(1) != 1 or h.stride(0) % 8:
         h = h.contiguous()
-    xq, xs = _quant(h)
-    _, ntf = dense_mxfp4_config(M, 2 * F_, H, "silu")
-    a = dense_mxfp4_gemm(xq, xs, w.gate_up_c, w.gate_up_e, w.gate_up_s, "silu", 1, ntf)
-    aq, as_ = _quant(a)
-    S, ntf = dense_mxfp4_config(M, H, F_, "slabs" if slabs else "bf16")
-    if slabs:
-        return Slabs(dense_mxfp4_gemm(aq, as_, w.down_c, w.down_e, w.down_s, "slabs", S, ntf)), a
-    return dense_mxfp4_gemm(aq, as_, w.down_c, w.down_e, w.down_s, "bf16", 1, ntf), a
+    return fp8_dense._mlp_stream(h, slabs, dense_mxfp4_config, dense_mxfp4_gemm,
+                                 (w.gate_up_c, w.gate_up_e, w.gate_up_s), (w.down_c, w.down_e, w.down_s))
 
 
 def _as_fp8(w: DenseMxfp4MLP) -> DenseFp8MLP:

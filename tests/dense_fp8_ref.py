@@ -1,4 +1,4 @@
-"""Host-side cases and references for the dense fp8 GEMM (``gemm_fp8_dense.hip``,
+"""Host-side cases and references for the dense fp8 GEMM (``gemm_dense_stream.hip``,
 ``ops.fp8_dense.dense_fp8_gemm``), in the style of ``decode_gemm_ref`` and ``moe_ref``.
 
 ``moe_ref`` records that the fp8 MFMAs accumulate in something narrower than f32, so the exact cases

@@ -1,4 +1,4 @@
-"""Host-side cases and references for the dense MXFP4 GEMM (``gemm_mxfp4_dense.hip``,
+"""Host-side cases and references for the dense MXFP4 GEMM (``gemm_dense_stream.hip``,
 ``ops.mxfp4_dense.dense_mxfp4_gemm``), on top of ``dense_fp8_ref``: its sentinel buffers, NaN-padded X
 rows, ``pow2``, ``OutBuf``, ``untouched`` and ``bits``.
 
