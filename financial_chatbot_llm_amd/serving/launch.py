@@ -165,7 +165,9 @@ def main(argv=None) -> int:
     from ..engine.llm_engine import LLMEngine
     from ..parallel.dist import init_cp_groups, init_distributed, shutdown
 
-    ps = init_distributed(tp_size=args.tp)
+    # --device decides the process group too: a CPU group is gloo even where a GPU is visible (RCCL
+    # refuses two ranks on one device)
+    ps = init_distributed(tp_size=args.tp, device_type=args.device)
     if args.cp > 1:
         ps = init_cp_groups(args.cp)
     dev_type = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
