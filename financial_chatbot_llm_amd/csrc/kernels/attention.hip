@@ -95,16 +95,17 @@ __device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const 
 // masking (all < ctx and, if causal, <= every row's position).
 // The masking is one wave-uniform branch around a select loop: a per-element `full || (...)`
 // short-circuit compiles to 32 divergent branches per block on gfx950.
-// MASK: 0 never, 1 always, 2 when the wave-uniform runtime flag `need_mask` is set.  Mode 2 keeps
-// ONE copy of the MFMA code in the loop: with two inlined copies (one per mode, behind an if/else)
-// the accumulators meet at a join point and hipcc materialises the merge as v_mov_b64 copies of
-// MFMA results (each one waits for its MFMA to retire), ~64 per block.
-template <int D, int MASK, bool PREF = false, bool SB = false>
+// `need_mask` is a wave-uniform runtime flag, so the loop holds ONE copy of the MFMA code: with two
+// inlined copies (masked and unmasked, behind an if/else) the accumulators meet at a join point and
+// hipcc materialises the merge as v_mov_b64 copies of MFMA results (each one waits for its MFMA to
+// retire), ~64 per block.
+// PREF: prefill2's variant 4 (the 4-wave kernel reads each fragment next to its MFMA), see below.
+template <int D, bool PREF>
 __device__ __forceinline__ void attend_block(const uint4* __restrict__ kl, const uint4* __restrict__ vl,
                                              const Frag (&qf)[2][D / 32], f32x4 (&o)[2][D / 16], float (&m)[2],
                                              float (&l)[2], bool causal, int j, int ctx,
                                              const int (&qpos)[2], float scale_log2, int lane, int g,
-                                             bool need_mask = false) {
+                                             bool need_mask) {
   constexpr int KC = D / 32;
   constexpr int DT = D / 16;
   // ---- S^T = K . Q^T for 64 keys x 32 query rows -------------------------------------
@@ -113,9 +114,9 @@ __device__ __forceinline__ void attend_block(const uint4* __restrict__ kl, const
   if constexpr (PREF) {
 #pragma unroll
     for (int f = 0; f < 4 * KC; ++f) kfa[f].u = kl[f * 64 + lane];
-    // SB: pin the 16 reads ahead of the MFMAs -- hipcc otherwise sinks each pair next to its use
+    // pin the 16 reads ahead of the MFMAs -- hipcc otherwise sinks each pair next to its use
     // and waits for it (lgkmcnt(0) every 2-4 MFMAs: the LDS latency exposed 8 times per block)
-    if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -137,12 +138,12 @@ __device__ __forceinline__ void attend_block(const uint4* __restrict__ kl, const
   if constexpr (PREF) {   // V fragments in flight while the softmax runs
 #pragma unroll
     for (int f = 0; f < 2 * DT; ++f) vfa[f].u = vl[f * 64 + lane];
-    if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 
   // ---- online softmax (base-2) -------------------------------------------------------
   Frag pf[2][2];
-  if (MASK == 1 || (MASK == 2 && need_mask)) {
+  if (need_mask) {
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -235,12 +236,12 @@ __device__ __forceinline__ void attend_block(const uint4* __restrict__ kl, const
 // ~17 log2 units: max error 0.08 vs the fp32 reference where the exact form holds 0.02) -- opt-in.
 // F8: kl / vl are e4m3 tiles (kv_layout.h): one ds_read_b128 delivers fragments 2p and 2p + 1, converted
 // to bf16 (kv_fp8_to_bf16x8, exact) into the same kfa / vfa registers the MFMAs read.
-template <int D, int MASK, bool SB = false, bool QPRE = false, bool F8 = false>
+template <int D, bool QPRE, bool F8>
 __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, const uint4* __restrict__ vl,
                                                   const Frag (&qf)[2][D / 32], f32x4 (&o)[2][D / 16],
                                                   float (&m)[2], f32x4 (&la)[2], bool causal, int j, int ctx,
                                                   const int (&qpos)[2], float scale_log2, int lane, int g,
-                                                  bool need_mask = false) {
+                                                  bool need_mask) {
   constexpr int KC = D / 32;
   constexpr int DT = D / 16;
   Frag kfa[4 * KC], vfa[2 * DT];
@@ -248,7 +249,7 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
     uint4 raw[2 * KC];
 #pragma unroll
     for (int p = 0; p < 2 * KC; ++p) raw[p] = kl[p * 64 + lane];
-    if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int p = 0; p < 2 * KC; ++p) {
       kfa[2 * p].v = kv_fp8_to_bf16x8(raw[p].x, raw[p].y);
@@ -257,7 +258,7 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
   } else {
 #pragma unroll
     for (int f = 0; f < 4 * KC; ++f) kfa[f].u = kl[f * 64 + lane];
-    if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
   // chains start at -m: the MFMAs deliver s*c - m (m = -inf, a row's first live block: start at 0,
   // and any finite max is a "rise")
@@ -287,9 +288,9 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
 #pragma unroll
     for (int f = 0; f < 2 * DT; ++f) vfa[f].u = vl[f * 64 + lane];
   }
-  if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_sched_barrier(0);
 
-  if (MASK == 1 || (MASK == 2 && need_mask)) {
+  if (need_mask) {
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -374,11 +375,10 @@ __device__ __forceinline__ void attend_block_fold(const uint4* __restrict__ kl, 
   }
 }
 
-template <int D>
-constexpr int prefill_smem_bytes() { return 4 * KV_BS * D * 2; }
-
 // One 128-row (token*G + head) tile of sequence `s`, kv head `h` (4 waves x 32 rows): the short-chunk
-// prefill path (<= 128 rows per sequence and kv head).
+// prefill path (<= 128 rows per sequence and kv head).  prefill_kernel's only caller, and kept apart
+// from it on purpose: written into the kernel body the same statements get another register
+// allocation and schedule (168 instead of 177 VGPRs at head dim 128) -- a change to measure on its own.
 template <int D>
 __device__ __forceinline__ void attend_tile(char* smem, const bf16* __restrict__ q, const int* __restrict__ cu_q,
                                             const int* __restrict__ ctx_lens, const int* __restrict__ block_tables,
@@ -419,7 +419,6 @@ __device__ __forceinline__ void attend_tile(char* smem, const bf16* __restrict__
   const int last_tok = min(tok0 + TQ, qlen) - 1;
   const int kv_end = causal ? min(ctx, ctx - qlen + last_tok + 1) : ctx;
   const int nblk = (kv_end + KV_BS - 1) / KV_BS;
-  const int jb = 0, je = nblk;
   const int* bt = block_tables + (long)s * max_blocks;
 
   f32x4 o[2][DT];
@@ -450,18 +449,18 @@ __device__ __forceinline__ void attend_tile(char* smem, const bf16* __restrict__
     }
   };
 
-  if (je > jb) stage(jb, 0);
+  if (nblk > 0) stage(0, 0);
   __syncthreads();
 
-  for (int j = jb; j < je; ++j) {
-    const int buf = (j - jb) & 1;
-    if (j + 1 < je) stage(j + 1, buf ^ 1);
+  for (int j = 0; j < nblk; ++j) {
+    const int buf = j & 1;
+    if (j + 1 < nblk) stage(j + 1, buf ^ 1);
     const uint4* kl = reinterpret_cast<const uint4*>(smem + buf * 2 * TILE);
     const uint4* vl = reinterpret_cast<const uint4*>(smem + buf * 2 * TILE + TILE);
 
     const bool full = (j + 1) * KV_BS <= ctx && (!causal || (j + 1) * KV_BS - 1 <= ctx - qlen + tok0);
-    attend_block<D, 2>(kl, vl, qf, o, m, l, causal, j, ctx, qpos, scale_log2, lane, g,
-                       __builtin_amdgcn_readfirstlane((int)!full) != 0);
+    attend_block<D, false>(kl, vl, qf, o, m, l, causal, j, ctx, qpos, scale_log2, lane, g,
+                           __builtin_amdgcn_readfirstlane((int)!full) != 0);
     __syncthreads();  // block j+1 landed (vmcnt drained) and everyone is done with buffer `buf`
   }
 
@@ -491,7 +490,7 @@ __global__ void __launch_bounds__(256, 2) prefill_kernel(
     const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
     bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
     float* __restrict__ lse) {
-  __shared__ __attribute__((aligned(16))) char smem[prefill_smem_bytes<D>()];  // [buf][K|V]
+  __shared__ __attribute__((aligned(16))) char smem[4 * KV_BS * D * 2];  // [buf][K|V]
   attend_tile<D>(smem, q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out, scale_log2, Hq, Hkv, max_blocks,
                  causal, blockIdx.z, blockIdx.y, blockIdx.x, lse);
 }
@@ -985,9 +984,9 @@ __global__ void __launch_bounds__(HPW * D) decode_lean_reduce_kernel(const int* 
 
 
 // Pipelined prefill (the production prefill path for tiles of > 128 rows).
-// One workgroup = NW waves x 32 rows = NW*32 (token*G + head) rows of one sequence and kv head:
-// every staged K/V block is shared by NW waves (half the LDS fill traffic per row of the 4-wave
-// tile) and the K/V ring is NBUF blocks deep, so block j+NBUF-1 streams in while block j is on
+// One workgroup = NW = 8 waves x 32 rows = 256 (token*G + head) rows of one sequence and kv head:
+// every staged K/V block is shared by 8 waves (half the LDS fill traffic per row of the 4-wave
+// tile) and the K/V ring is NBUF = 3 blocks deep, so block j+2 streams in while block j is on
 // the MFMAs.  Synchronisation follows the counted-vmcnt recipe: each wave waits only for ITS
 // pieces of block j (`s_waitcnt vmcnt(LOADS)` while the next block's pieces stay in flight), one
 // raw s_barrier publishes block j to all waves and retires everyone's reads of the buffer about
@@ -1015,7 +1014,9 @@ struct PrefillLean {
 // and the counted vmcnt waits below halve with it.  kv_scales [2, Hkv] f32 or null (= 1): K's scale
 // folds into scale_log2 (m, the partial m and lse are then in units of the true scores); V's scale
 // into inv / pinv, once on either path (the merge kernel sees partials that already carry it).
-template <int D, int NW, int NBUF, bool HEAD_FAST, bool PREF, bool SB, int FOLD, bool F8>
+// FOLD: the block loop -- 0 attend_block with its fragment prefetch (variant 4), 1 attend_block_fold
+// with exact Q (variant 5), 2 the same with Q prescaled in-kernel (variant 6, and every prescaled-Q call).
+template <int D, int FOLD, bool F8>
 __device__ __forceinline__ void prefill2_body(
     const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
@@ -1023,6 +1024,7 @@ __device__ __forceinline__ void prefill2_body(
     float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean,
     const float* __restrict__ kv_scales) {
   constexpr int KC = D / 32, DT = D / 16;
+  constexpr int NW = 8, NBUF = 3;             // waves per workgroup, K/V ring depth
   static_assert(!F8 || FOLD == 1, "the fp8 cache is ported to the FOLD = 1 block loop only");
   constexpr int TILE = KV_BS * D * (F8 ? 1 : 2);   // bytes of one K (or V) block tile
   constexpr int PIECES = TILE / 1024 / NW;    // 1-KiB glds pieces per wave per tile
@@ -1031,18 +1033,18 @@ __device__ __forceinline__ void prefill2_body(
   __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * TILE];  // [buf][K|V]
 
   // causal tiles grow with their index: dispatch the longest first so they do not form the tail.
-  // HEAD_FAST grid (Hkv, tiles, seqs): with round-robin dispatch over the 8 XCDs every tile of a
+  // Head-fastest grid (Hkv, tiles, seqs): with round-robin dispatch over the 8 XCDs every tile of a
   // (sequence, kv head) lands on the same XCD, so its K/V blocks are fetched into one L2 and
   // re-read from there by the other tiles (grid (tiles, Hkv, seqs) spreads them over all 8 L2s)
   // `work` (host-built, ops.attention.prefill_work_list): the step's real (sequence, tile) pairs,
   // longest KV walk first across ALL sequences (LPT order: the short decide tiles fill the last
   // round instead of trailing it, and no workgroup is launched for a tile past a short sequence's
   // end).  Without it: grid (.., max tiles, sequences), each sequence's tiles longest first.
-  const int item = HEAD_FAST ? blockIdx.y : blockIdx.x;
+  const int item = blockIdx.y;
   const int* li = lean.items ? lean.items + 6 * item : nullptr;
   const int s = li ? li[0] : (work ? work[2 * item] : blockIdx.z);
-  const int h = HEAD_FAST ? blockIdx.x : blockIdx.y;
-  const int tile = li ? li[1] : (work ? work[2 * item + 1] : (HEAD_FAST ? gridDim.y : gridDim.x) - 1 - item);
+  const int h = blockIdx.x;
+  const int tile = li ? li[1] : (work ? work[2 * item + 1] : gridDim.y - 1 - item);
   const int G = Hq / Hkv;
   const int TQ = NW * 32 / G;
   const int q0 = cu_q[s], qlen = cu_q[s + 1] - q0;
@@ -1139,7 +1141,7 @@ __device__ __forceinline__ void prefill2_body(
   const int wave_kv_end = causal ? ctx - qlen + wave_last + 1 : ctx;
   for (int j = 0; j < nblk; ++j) {           // local block j = absolute block jb + j
     // my pieces of block j landed (younger blocks j+1.. may stay in flight), then publish
-    if (j + NBUF - 2 < nblk && NBUF >= 3) wait_vmcnt_barrier<(NBUF - 2) * LOADS>();
+    if (j + NBUF - 2 < nblk) wait_vmcnt_barrier<(NBUF - 2) * LOADS>();
     else wait_vmcnt_barrier<0>();
     if (j + NBUF - 1 < nblk) stage(j + NBUF - 1);   // refills the buffer everyone finished at j-1
     const int ja = jb + j;
@@ -1148,11 +1150,11 @@ __device__ __forceinline__ void prefill2_body(
     const uint4* vl = reinterpret_cast<const uint4*>(smem + (j % NBUF) * 2 * TILE + TILE);
     const bool full = (ja + 1) * KV_BS <= ctx && (!causal || (ja + 1) * KV_BS - 1 <= ctx - qlen + wave_tok0);
     if constexpr (FOLD != 0)
-      attend_block_fold<D, 2, SB, FOLD == 2, F8>(kl, vl, qf, o, m, la, causal, ja, ctx, qpos, scale_log2, lane, g,
-                                                 __builtin_amdgcn_readfirstlane((int)!full) != 0);
+      attend_block_fold<D, FOLD == 2, F8>(kl, vl, qf, o, m, la, causal, ja, ctx, qpos, scale_log2, lane, g,
+                                          __builtin_amdgcn_readfirstlane((int)!full) != 0);
     else
-      attend_block<D, 2, PREF, SB>(kl, vl, qf, o, m, l, causal, ja, ctx, qpos, scale_log2, lane, g,
-                                   __builtin_amdgcn_readfirstlane((int)!full) != 0);
+      attend_block<D, true>(kl, vl, qf, o, m, l, causal, ja, ctx, qpos, scale_log2, lane, g,
+                            __builtin_amdgcn_readfirstlane((int)!full) != 0);
   }
 
 #pragma unroll
@@ -1189,27 +1191,25 @@ __device__ __forceinline__ void prefill2_body(
   }
 }
 
-template <int D, int NW, int NBUF, bool HEAD_FAST, bool PREF = true, bool SB = false, int FOLD = 0>
-__global__ void __launch_bounds__(NW * 64, 1) prefill2_kernel(
+template <int D, int FOLD>
+__global__ void __launch_bounds__(512, 1) prefill2_kernel(
     const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
     bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
     float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean = PrefillLean{}) {
-  prefill2_body<D, NW, NBUF, HEAD_FAST, PREF, SB, FOLD, false>(q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out,
-                                                               scale_log2, Hq, Hkv, max_blocks, causal, lse, work,
-                                                               lean, nullptr);
+  prefill2_body<D, FOLD, false>(q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out, scale_log2, Hq, Hkv,
+                                max_blocks, causal, lse, work, lean, nullptr);
 }
 
-// the fp8 (e4m3) cache instantiation: head dim 128, 8 waves, 3 buffers, the FOLD = 1 block loop
+// the fp8 (e4m3) cache instantiation: head dim 128, the FOLD = 1 block loop
 __global__ void __launch_bounds__(512, 1) prefill2_fp8_kernel(
     const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
     bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
     float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean,
     const float* __restrict__ kv_scales) {
-  prefill2_body<128, 8, 3, true, true, true, 1, true>(q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out,
-                                                      scale_log2, Hq, Hkv, max_blocks, causal, lse, work, lean,
-                                                      kv_scales);
+  prefill2_body<128, 1, true>(q, cu_q, ctx_lens, block_tables, k_cache, v_cache, out, scale_log2, Hq, Hkv,
+                              max_blocks, causal, lse, work, lean, kv_scales);
 }
 
 // Merge the chunk partials of split tiles (lean prefill): grid (splits, Hkv, 256 / RPB), 256
@@ -1404,13 +1404,13 @@ __device__ __forceinline__ void attend_block32(const char* __restrict__ kl, cons
 }
 
 // prefill2_kernel's grid, work lists, lean slots and K/V staging ring with attend_block32 (D = 128)
-template <int NBUF, bool QPRE>
+template <bool QPRE>
 __global__ void __launch_bounds__(512, 1) prefill3_kernel(
     const bf16* __restrict__ q, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ block_tables, const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
     bf16* __restrict__ out, float scale_log2, int Hq, int Hkv, int max_blocks, int causal,
     float* __restrict__ lse, const int* __restrict__ work, PrefillLean lean = PrefillLean{}) {
-  constexpr int D = 128, NW = 8;
+  constexpr int D = 128, NW = 8, NBUF = 3;
   constexpr int TILE = KV_BS * D * 2;
   constexpr int PIECES = TILE / 1024 / NW;
   constexpr int LOADS = 2 * PIECES;
@@ -1493,7 +1493,7 @@ __global__ void __launch_bounds__(512, 1) prefill3_kernel(
   // partner on every segment otherwise; cdna_hip_programming.md T5 static form)
   if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
   for (int jj = 0; jj < nblk; ++jj) {
-    if (jj + NBUF - 2 < nblk && NBUF >= 3) wait_vmcnt_barrier<(NBUF - 2) * LOADS>();
+    if (jj + NBUF - 2 < nblk) wait_vmcnt_barrier<(NBUF - 2) * LOADS>();
     else wait_vmcnt_barrier<0>();
     if (jj + NBUF - 1 < nblk) stage(jj + NBUF - 1);
     const int ja = jb + jj;
@@ -1542,57 +1542,10 @@ __global__ void __launch_bounds__(512, 1) prefill3_kernel(
     lse[(long)(q0 + tok) * Hq + head] = lt > 0.f ? (m + __log2f(lt)) * 0.6931471805599453f : -INFINITY;
 }
 
-static int prefill_variant();
-
-// Lean big-tile prefill: items [nitems, 6] (see PrefillLean; LPT order), merge [nmerge, 6];
-// part_o / part_ml sized for the slots the items use.  Runs prefill2 in the selected variant.
-PENNY_API int penny_attention_prefill_lean(const void* q, const int* cu_q, const int* ctx_lens, const int* block_tables,
-                                           const void* k_cache, const void* v_cache, void* out, int Hq, int Hkv,
-                                           int D, int max_blocks, float scale, int causal, float* lse,
-                                           const int* items, int nitems, const int* merge, int nmerge,
-                                           void* part_o, float* part_ml, hipStream_t stream) {
-  if (nitems <= 0) return 0;
-  if (Hq % Hkv || (256 % (Hq / Hkv)) || !items || (nmerge > 0 && (!merge || !part_o || !part_ml)))
-    return (int)hipErrorInvalidValue;
-  // causal bit 1: q arrives prescaled by scale * log2(e) (penny_gemm_prefill_qkv_rope qscale)
-  const bool qpre = causal & 2;
-  causal &= 1;
-  const float sl2 = qpre ? 1.f : scale * LOG2E;
-  const PrefillLean lean{items, static_cast<bf16*>(part_o), part_ml};
-  const int var = prefill_variant();
-  const dim3 grid(Hkv, nitems, 1);
-#define LEAN_LAUNCH(DD, PREF_, SB_, FOLD_)                                                                        \
-  hipLaunchKernelGGL((prefill2_kernel<DD, 8, 3, true, PREF_, SB_, FOLD_>), grid, dim3(512), 0, stream,             \
-                     (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,       \
-                     (bf16*)out, sl2, Hq, Hkv, max_blocks, causal, lse, (const int*)nullptr, lean)
-#define LEAN_VARIANTS(DD)                                   \
-  if (DD == 128 && var == 7) {                              \
-    if (qpre)                                               \
-      hipLaunchKernelGGL((prefill3_kernel<3, true>), grid, dim3(512), 0, stream, (const bf16*)q, cu_q, ctx_lens, \
-                         block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, sl2, Hq, Hkv,   \
-                         max_blocks, causal, lse, (const int*)nullptr, lean);                                  \
-    else                                                    \
-      hipLaunchKernelGGL((prefill3_kernel<3, false>), grid, dim3(512), 0, stream, (const bf16*)q, cu_q, ctx_lens, \
-                         block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, sl2, Hq, Hkv,    \
-                         max_blocks, causal, lse, (const int*)nullptr, lean);                                   \
-  } else if (var == 6 || qpre) LEAN_LAUNCH(DD, true, true, 2); \
-  else if (var == 4) LEAN_LAUNCH(DD, true, true, 0);        \
-  else LEAN_LAUNCH(DD, true, true, 1);                      \
-  if (nmerge > 0)                                           \
-    hipLaunchKernelGGL(prefill_merge_kernel<DD>, dim3(nmerge, Hkv, 256 / (4 * (64 / (DD / 4)))), dim3(256), 0, stream, \
-                       merge, cu_q, static_cast<const bf16*>(part_o), part_ml, (bf16*)out, lse, Hq, Hkv);
-  if (D == 128) {
-    LEAN_VARIANTS(128)
-  } else if (D == 64) {
-    LEAN_VARIANTS(64)
-  } else {
-    return (int)hipErrorInvalidValue;
-  }
-#undef LEAN_VARIANTS
-#undef LEAN_LAUNCH
-  PENNY_RETURN_LAUNCH();
-}
-
+// ------------------------------------------------------------------------------------------
+// Host side: one entry point per operation.  fp8 (e4m3) caches are announced by an explicit flag,
+// never inferred from kv_scales ([2, Hkv] f32: K heads, then V heads), whose null means scale 1.
+// ------------------------------------------------------------------------------------------
 // Big-tile prefill variant (PENNY_PREFILL_PP, or penny_attention_prefill_variant for in-process A/B
 // runs): 7 (default, r6) prefill3 -- the block math on v_mfma_f32_32x32x16_bf16 (head dim 128; 64
 // takes 5): +3-5 % on the workload's mixed respond + decide / spec steps, -1-3 % on long single
@@ -1618,84 +1571,125 @@ PENNY_API int penny_attention_prefill_variant(int v) {
   return old;
 }
 
+// what every prefill kernel takes, in the kernels' parameter order
+struct PrefillArgs {
+  const bf16* q;
+  const int *cu_q, *ctx_lens, *block_tables;
+  const bf16 *k_cache, *v_cache;
+  bf16* out;
+  float scale_log2;
+  int Hq, Hkv, max_blocks, causal;
+  float* lse;
+};
+
+// The big-tile (256-row) kernel of the variant.  fp8 cache: always prefill2 in its FOLD = 1 form,
+// whatever the variant (prefill3 and the other block loops are not ported).  Variant 7 is prefill3 at
+// head dim 128 and falls to prefill2 at 64; prescaled Q selects prefill3<true> under 7 and prefill2's
+// FOLD = 2 loop otherwise, also when the variant says 4 or 5 (the loop multiplies by 1: the exact
+// scores of variant 5 without its per-score FMA).
+template <int D>
+static void launch_prefill_big(int variant, bool qpre, bool fp8, dim3 grid, const PrefillArgs& a, const int* work,
+                               PrefillLean lean, const float* kv_scales, hipStream_t stream) {
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(512), 0, stream, a.q, a.cu_q, a.ctx_lens, a.block_tables, a.k_cache,
+                       a.v_cache, a.out, a.scale_log2, a.Hq, a.Hkv, a.max_blocks, a.causal, a.lse, work, lean);
+  };
+  if constexpr (D == 128) {
+    if (fp8) {
+      hipLaunchKernelGGL(prefill2_fp8_kernel, grid, dim3(512), 0, stream, a.q, a.cu_q, a.ctx_lens, a.block_tables,
+                         a.k_cache, a.v_cache, a.out, a.scale_log2, a.Hq, a.Hkv, a.max_blocks, a.causal, a.lse, work,
+                         lean, kv_scales);
+      return;
+    }
+    if (variant == 7) {
+      if (qpre) launch(prefill3_kernel<true>);
+      else launch(prefill3_kernel<false>);
+      return;
+    }
+  }
+  if (variant == 6 || qpre) launch(prefill2_kernel<D, 2>);
+  else if (variant == 4) launch(prefill2_kernel<D, 0>);
+  else launch(prefill2_kernel<D, 1>);
+}
+
+template <int D>
+static void launch_prefill_merge(const int* merge, int nmerge, const PrefillArgs& a, PrefillLean lean,
+                                 hipStream_t stream) {
+  constexpr int RPB = 4 * (64 / (D / 4));   // rows per workgroup (prefill_merge_kernel)
+  hipLaunchKernelGGL(prefill_merge_kernel<D>, dim3(nmerge, a.Hkv, 256 / RPB), dim3(256), 0, stream, merge, a.cu_q,
+                     static_cast<const bf16*>(lean.part_o), lean.part_ml, a.out, a.lse, a.Hq, a.Hkv);
+}
+
+// flags: bit 0 causal; bit 1 q arrives prescaled by scale * log2(e) at its one bf16 rounding (the fused
+// QKV epilogue's qscale, penny_gemm_prefill_qkv_rope); bit 2 the cache is e4m3 (head dim 128, causal,
+// exact Q only: anything else is refused).
+// work [nwork, work_cols]: work_cols 0 none -- the full grid; 2 prefill_work_list's (sequence, tile)
+// pairs of the 256-row tiles, LPT order (big tiles only); 6 the lean list (see PrefillLean; LPT order)
+// with merge [nmerge, 6] and part_o / part_ml sized for the slots the items use (num_seqs and
+// max_q_len are not read).
 PENNY_API int penny_attention_prefill(const void* q, const int* cu_q, const int* ctx_lens, const int* block_tables,
                                       const void* k_cache, const void* v_cache, void* out, int num_seqs,
-                                      int max_q_len, int Hq, int Hkv, int D, int max_blocks, float scale, int causal,
-                                      float* lse, const int* work, int nwork, hipStream_t stream) {
-  if (num_seqs <= 0 || max_q_len <= 0) return 0;
-  if (Hq % Hkv) return (int)hipErrorInvalidValue;
+                                      int max_q_len, int Hq, int Hkv, int D, int max_blocks, float scale, int flags,
+                                      float* lse, const int* work, int nwork, int work_cols, const int* merge,
+                                      int nmerge, void* part_o, float* part_ml, const float* kv_scales,
+                                      hipStream_t stream) {
+  const bool items = work_cols == 6, qpre = flags & 2, fp8 = flags & 4;
+  if (items ? nwork <= 0 : (num_seqs <= 0 || max_q_len <= 0)) return 0;
+  if ((D != 128 && D != 64) || (work_cols != 0 && work_cols != 2 && !items) || Hkv <= 0 || Hq % Hkv)
+    return (int)hipErrorInvalidValue;
   const int G = Hq / Hkv;
-  if (G > 128 || (128 % G)) return (int)hipErrorInvalidValue;
-  // causal bit 1: q arrives prescaled by scale * log2(e) at its one bf16 rounding (the fused QKV
-  // epilogue's qscale): the big tiles then run the prescaled-Q fold (variant 6's loop without its
-  // in-kernel re-rounding of q * c -- it multiplies by 1), the exact scores of variant 5
-  const bool qpre = causal & 2;
-  causal &= 1;
-  const float sl2 = qpre ? 1.f : scale * LOG2E;
-  // > 128 rows per (sequence, kv head): the 8-wave pipelined kernel; short chunks keep the
-  // 4-wave tile (a 256-row tile would be mostly padding)
-  const bool big = (long)max_q_len * G > 128;
-  const int pp_env = prefill_variant();
+  if (fp8 && (D != 128 || flags != 5)) return (int)hipErrorInvalidValue;
+  if (items ? (256 % G || !work || (nmerge > 0 && (!merge || !part_o || !part_ml)))
+            : (fp8 ? 256 % G : (G > 128 || 128 % G)))
+    return (int)hipErrorInvalidValue;
+  // > 128 rows per (sequence, kv head): the 8-wave pipelined kernels; short chunks keep the 4-wave
+  // tile (a 256-row tile would be mostly padding) -- except on an fp8 cache, which has no other kernel
+  const bool big = items || fp8 || (long)max_q_len * G > 128;
   const int TQ = (big ? 256 : 128) / G;
   const int ntiles = (max_q_len + TQ - 1) / TQ;
-  // grid (Hkv, tiles, seqs): the kv head is the fastest workgroup index, so with round-robin dispatch
-  // over the 8 XCDs each XCD owns one kv head (+5-47 % TF/s over tile-fastest,
-  // profiles/r1_prefill_head_fast.txt: 457 -> 672 at 4 x 2048 causal, 687 -> 905 at 1 x 8192)
-  // work list (big tiles only): one workgroup per real (sequence, tile), LPT order
-  const bool wl = big && work != nullptr && nwork > 0;
-  const dim3 grid(ntiles, Hkv, num_seqs);
-  const dim3 grid2 = wl ? dim3(Hkv, nwork, 1) : dim3(Hkv, ntiles, num_seqs);
-  const int* wp = wl ? work : nullptr;
-#define PREFILL_LAUNCH(DD)                                                                                       \
-  if (big && DD == 128 && pp_env == 7) {                                                                         \
-    if (qpre)                                                                                                    \
-      hipLaunchKernelGGL((prefill3_kernel<3, true>), grid2, dim3(512), 0, stream, (const bf16*)q, cu_q, ctx_lens,  \
-                         block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, sl2, Hq, Hkv,     \
-                         max_blocks, causal, lse, wp);                                                           \
-    else                                                                                                         \
-      hipLaunchKernelGGL((prefill3_kernel<3, false>), grid2, dim3(512), 0, stream, (const bf16*)q, cu_q, ctx_lens, \
-                         block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, sl2, Hq, Hkv,      \
-                         max_blocks, causal, lse, wp);                                                            \
-  } else if (big && (pp_env == 6 || qpre))                                                                       \
-    hipLaunchKernelGGL((prefill2_kernel<DD, 8, 3, true, true, true, 2>), grid2, dim3(512), 0, stream,            \
-                       (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,   \
-                       (bf16*)out, sl2, Hq, Hkv, max_blocks, causal, lse, wp);                                     \
-  else if (big && pp_env == 4)                                                                                   \
-    hipLaunchKernelGGL((prefill2_kernel<DD, 8, 3, true, true, true>), grid2, dim3(512), 0, stream,               \
-                       (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,   \
-                       (bf16*)out, sl2, Hq, Hkv, max_blocks, causal, lse, wp);                                     \
-  else if (big)                                                                                                  \
-    hipLaunchKernelGGL((prefill2_kernel<DD, 8, 3, true, true, true, 1>), grid2, dim3(512), 0, stream,            \
-                       (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,   \
-                       (bf16*)out, sl2, Hq, Hkv, max_blocks, causal, lse, wp);                                     \
-  else                                                                                                           \
-    hipLaunchKernelGGL(prefill_kernel<DD>, grid, dim3(256), 0, stream, (const bf16*)q, cu_q, ctx_lens,           \
-                       block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, sl2, Hq, Hkv,         \
-                       max_blocks, causal, lse);
-  if (D == 128) {
-    PREFILL_LAUNCH(128)
-  } else if (D == 64) {
-    PREFILL_LAUNCH(64)
-  } else {
-    return (int)hipErrorInvalidValue;
-  }
-#undef PREFILL_LAUNCH
+  const PrefillArgs a{(const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,
+                      (bf16*)out, qpre ? 1.f : scale * LOG2E, Hq, Hkv, max_blocks, flags & 1, lse};
+  // big tiles: grid (Hkv, tiles, seqs) -- the kv head is the fastest workgroup index, so with round-robin
+  // dispatch over the 8 XCDs each XCD owns one kv head (+5-47 % TF/s over tile-fastest,
+  // profiles/r1_prefill_head_fast.txt: 457 -> 672 at 4 x 2048 causal, 687 -> 905 at 1 x 8192) -- or,
+  // with a work list or lean items, one workgroup per listed (sequence, tile[, chunk])
+  const bool listed = items || (big && work_cols == 2 && work != nullptr && nwork > 0);
+  const dim3 grid = !big ? dim3(ntiles, Hkv, num_seqs) : listed ? dim3(Hkv, nwork, 1) : dim3(Hkv, ntiles, num_seqs);
+  const PrefillLean lean = items ? PrefillLean{work, static_cast<bf16*>(part_o), part_ml} : PrefillLean{};
+  const int variant = prefill_variant();
+  auto run = [&](auto dc) {
+    constexpr int DD = decltype(dc)::value;
+    if (!big) {
+      hipLaunchKernelGGL(prefill_kernel<DD>, grid, dim3(256), 0, stream, a.q, a.cu_q, a.ctx_lens, a.block_tables,
+                         a.k_cache, a.v_cache, a.out, a.scale_log2, a.Hq, a.Hkv, a.max_blocks, a.causal, a.lse);
+      return;
+    }
+    launch_prefill_big<DD>(variant, qpre, fp8, grid, a, listed && !items ? work : nullptr, lean, kv_scales, stream);
+    if (items && nmerge > 0) launch_prefill_merge<DD>(merge, nmerge, a, lean, stream);
+  };
+  if (D == 128) run(std::integral_constant<int, 128>{});
+  else run(std::integral_constant<int, 64>{});
   PENNY_RETURN_LAUNCH();
 }
 
+// lean_grid > 0: the work-balanced kernel (decode_lean_kernel) and its merge; otherwise the
+// per-(row, head, partition) kernel, kept as the fallback (PENNY_DECODE_LEAN=0).  fp8 != 0: the cache
+// is e4m3 -- head dim 128 and the lean kernel only (the fallback kernel is not ported).
 PENNY_API int penny_attention_decode(const void* q, const int* ctx_lens, const int* block_tables, const void* k_cache,
                                      const void* v_cache, void* out, float* part_m, float* part_l, float* part_o,
                                      int B, int Hq, int Hkv, int D, int max_blocks, int pb, int nparts,
                                      int part_stride, float scale, int lean_grid, int* lean_meta,
-                                     int lean_min_per_wave, int lean_flags, hipStream_t stream) {
+                                     int lean_min_per_wave, int lean_flags, const float* kv_scales, int fp8,
+                                     hipStream_t stream) {
   if (B <= 0) return 0;
-  if (Hq % Hkv || Hq / Hkv > 16 || pb <= 0 || nparts <= 0 || part_stride < nparts) return (int)hipErrorInvalidValue;
-  // lean_grid > 0: the work-balanced kernel (decode_lean_kernel) and its merge; otherwise the
-  // per-(row, head, partition) kernel, kept as the fallback (PENNY_DECODE_LEAN=0)
+  if ((D != 128 && D != 64) || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 16 || pb <= 0 || nparts <= 0 ||
+      part_stride < nparts)
+    return (int)hipErrorInvalidValue;
   const bool lean = lean_grid > 0;
   if (lean && (B > LEAN_MAX_B || nparts < 2 || !lean_meta || lean_min_per_wave < 1 || lean_grid % Hkv ||
                Hkv > LEAN_META0))
     return (int)hipErrorInvalidValue;
+  if (fp8 && (D != 128 || !lean)) return (int)hipErrorInvalidValue;
   // measured (profiles/r1_decode_head_fast.txt): head-fastest wins at B <= 16 (18.5 vs 21.6 us at
   // ctx 2048 / 1024 shared), sequence-fastest at B >= 64 (a sequence's 8 heads of a KV block are
   // one contiguous 128 KB run, read by one XCD); PENNY_DECODE_HEAD_FAST=0/1 forces either
@@ -1704,123 +1698,44 @@ PENNY_API int penny_attention_decode(const void* q, const int* ctx_lens, const i
     return v ? atoi(v) : -1;
   }();
   const bool head_fast = head_fast_env >= 0 ? head_fast_env != 0 : B <= 16;
-  const dim3 grid = head_fast ? dim3(Hkv, B, nparts) : dim3(B, nparts, Hkv);
   const float sl2 = scale * LOG2E;
-#define DECODE_LAUNCH(DD)                                                                                         \
-  if (lean) {                                                                                                   \
-    if (lean_flags & 1)                                                                                         \
-      hipLaunchKernelGGL((decode_lean_kernel<DD, true>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q,  \
-                         ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m,  \
-                         part_l, part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride,            \
-                         lean_min_per_wave, (const float*)nullptr);                                              \
-    else                                                                                                        \
-      hipLaunchKernelGGL((decode_lean_kernel<DD, false>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q, \
-                         ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m,  \
-                         part_l, part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride,            \
-                         lean_min_per_wave, (const float*)nullptr);                                              \
-    if (lean_flags & 2)                                                                                         \
-      hipLaunchKernelGGL((decode_lean_reduce_kernel<DD, 4>), dim3((Hq + 3) / 4, B), dim3(4 * DD), 0, stream,     \
-                         lean_meta, part_m, part_l, part_o, (bf16*)out, B, Hq, part_stride);                      \
-    else                                                                                                        \
-      hipLaunchKernelGGL((decode_lean_reduce_kernel<DD, 1>), dim3(Hq, B), dim3(DD), 0, stream, lean_meta, part_m, \
-                         part_l, part_o, (bf16*)out, B, Hq, part_stride);                                         \
-  } else {                                                                                                      \
-    if (head_fast)                                                                                              \
-      hipLaunchKernelGGL((decode_kernel<DD, true>), grid, dim3(256), 0, stream, (const bf16*)q, ctx_lens,          \
-                         block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m, part_l,   \
-                         part_o, sl2, Hq, Hkv, max_blocks, pb, nparts, part_stride);                              \
-    else                                                                                                        \
-      hipLaunchKernelGGL((decode_kernel<DD, false>), grid, dim3(256), 0, stream, (const bf16*)q, ctx_lens,         \
-                         block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m, part_l,   \
-                         part_o, sl2, Hq, Hkv, max_blocks, pb, nparts, part_stride);                              \
-    if (nparts > 1)                                                                                             \
-      hipLaunchKernelGGL(decode_reduce_kernel<DD>, dim3(Hq, B), dim3(DD), 0, stream, ctx_lens, part_m, part_l,     \
-                         part_o, (bf16*)out, Hq, pb, nparts, part_stride);                                        \
-  }
-  if (D == 128) {
-    DECODE_LAUNCH(128)
-  } else if (D == 64) {
-    DECODE_LAUNCH(64)
-  } else {
-    return (int)hipErrorInvalidValue;
-  }
-#undef DECODE_LAUNCH
-  PENNY_RETURN_LAUNCH();
-}
-
-// ------------------------------------------------------------------------------------------
-// fp8 (e4m3) KV cache entry points: head dim 128, kv_scales [2, Hkv] f32 (K heads, then V heads) or
-// null for 1.  The bf16 entry points above are unchanged.
-// ------------------------------------------------------------------------------------------
-// Lean decode only: the per-(row, head, partition) fallback kernel is not ported.
-PENNY_API int penny_attention_decode_fp8(const void* q, const int* ctx_lens, const int* block_tables,
-                                         const void* k_cache, const void* v_cache, void* out, float* part_m,
-                                         float* part_l, float* part_o, int B, int Hq, int Hkv, int D, int max_blocks,
-                                         int nparts, int part_stride, float scale, int lean_grid, int* lean_meta,
-                                         int lean_min_per_wave, int lean_flags, const float* kv_scales,
-                                         hipStream_t stream) {
-  if (B <= 0) return 0;
-  if (D != 128 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 16 || nparts < 2 || part_stride < nparts || lean_grid <= 0 ||
-      B > LEAN_MAX_B || !lean_meta || lean_min_per_wave < 1 || lean_grid % Hkv || Hkv > LEAN_META0)
-    return (int)hipErrorInvalidValue;
-  const float sl2 = scale * LOG2E;
-  if (lean_flags & 1)
-    hipLaunchKernelGGL((decode_lean_kernel<128, true, true>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q,
-                       ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m, part_l,
-                       part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride, lean_min_per_wave,
-                       kv_scales);
-  else
-    hipLaunchKernelGGL((decode_lean_kernel<128, false, true>), dim3(lean_grid), dim3(256), 0, stream, (const bf16*)q,
-                       ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache, (bf16*)out, part_m, part_l,
-                       part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride, lean_min_per_wave,
-                       kv_scales);
-  if (lean_flags & 2)
-    hipLaunchKernelGGL((decode_lean_reduce_kernel<128, 4>), dim3((Hq + 3) / 4, B), dim3(4 * 128), 0, stream, lean_meta,
-                       part_m, part_l, part_o, (bf16*)out, B, Hq, part_stride);
-  else
-    hipLaunchKernelGGL((decode_lean_reduce_kernel<128, 1>), dim3(Hq, B), dim3(128), 0, stream, lean_meta, part_m,
-                       part_l, part_o, (bf16*)out, B, Hq, part_stride);
-  PENNY_RETURN_LAUNCH();
-}
-
-// Always prefill2 in its FOLD = 1 form on 256-row tiles, whatever PENNY_PREFILL_PP says and however
-// short the chunks are (the 4-wave short-chunk kernel and prefill3 are not ported); causal only.
-// `work`: prefill_work_list's (sequence, tile) pairs for 256-row tiles, or null for the full grid.
-PENNY_API int penny_attention_prefill_fp8(const void* q, const int* cu_q, const int* ctx_lens,
-                                          const int* block_tables, const void* k_cache, const void* v_cache,
-                                          void* out, int num_seqs, int max_q_len, int Hq, int Hkv, int D,
-                                          int max_blocks, float scale, int causal, float* lse, const int* work,
-                                          int nwork, const float* kv_scales, hipStream_t stream) {
-  if (num_seqs <= 0 || max_q_len <= 0) return 0;
-  if (D != 128 || causal != 1 || Hkv <= 0 || Hq % Hkv || 256 % (Hq / Hkv)) return (int)hipErrorInvalidValue;
-  const int TQ = 256 / (Hq / Hkv);
-  const int ntiles = (max_q_len + TQ - 1) / TQ;
-  const bool wl = work != nullptr && nwork > 0;
-  const dim3 grid = wl ? dim3(Hkv, nwork, 1) : dim3(Hkv, ntiles, num_seqs);
-  hipLaunchKernelGGL(prefill2_fp8_kernel, grid, dim3(512), 0, stream,
-                     (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache, (const bf16*)v_cache,
-                     (bf16*)out, scale * LOG2E, Hq, Hkv, max_blocks, 1, lse, wl ? work : (const int*)nullptr,
-                     PrefillLean{}, kv_scales);
-  PENNY_RETURN_LAUNCH();
-}
-
-PENNY_API int penny_attention_prefill_lean_fp8(const void* q, const int* cu_q, const int* ctx_lens,
-                                               const int* block_tables, const void* k_cache, const void* v_cache,
-                                               void* out, int Hq, int Hkv, int D, int max_blocks, float scale,
-                                               int causal, float* lse, const int* items, int nitems,
-                                               const int* merge, int nmerge, void* part_o, float* part_ml,
-                                               const float* kv_scales, hipStream_t stream) {
-  if (nitems <= 0) return 0;
-  if (D != 128 || causal != 1 || Hkv <= 0 || Hq % Hkv || (256 % (Hq / Hkv)) || !items ||
-      (nmerge > 0 && (!merge || !part_o || !part_ml)))
-    return (int)hipErrorInvalidValue;
-  const PrefillLean lean{items, static_cast<bf16*>(part_o), part_ml};
-  hipLaunchKernelGGL(prefill2_fp8_kernel, dim3(Hkv, nitems, 1), dim3(512), 0,
-                     stream, (const bf16*)q, cu_q, ctx_lens, block_tables, (const bf16*)k_cache,
-                     (const bf16*)v_cache, (bf16*)out, scale * LOG2E, Hq, Hkv, max_blocks, 1, lse,
-                     (const int*)nullptr, lean, kv_scales);
-  if (nmerge > 0)
-    hipLaunchKernelGGL(prefill_merge_kernel<128>, dim3(nmerge, Hkv, 256 / (4 * (64 / (128 / 4)))), dim3(256), 0, stream,
-                       merge, cu_q, static_cast<const bf16*>(part_o), part_ml, (bf16*)out, lse, Hq, Hkv);
+  const bf16 *qb = (const bf16*)q, *kc = (const bf16*)k_cache, *vc = (const bf16*)v_cache;
+  bf16* ob = (bf16*)out;
+  auto run = [&](auto dc) {
+    constexpr int DD = decltype(dc)::value;
+    if (lean) {
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(lean_grid), dim3(256), 0, stream, qb, ctx_lens, block_tables, kc, vc, ob,
+                           part_m, part_l, part_o, lean_meta, sl2, B, Hq, Hkv, max_blocks, nparts, part_stride,
+                           lean_min_per_wave, kv_scales);
+      };
+      const bool nt = lean_flags & 1;
+      if (!fp8) {
+        if (nt) launch(decode_lean_kernel<DD, true, false>);
+        else launch(decode_lean_kernel<DD, false, false>);
+      } else if constexpr (DD == 128) {
+        if (nt) launch(decode_lean_kernel<128, true, true>);
+        else launch(decode_lean_kernel<128, false, true>);
+      }
+      if (lean_flags & 2)
+        hipLaunchKernelGGL((decode_lean_reduce_kernel<DD, 4>), dim3((Hq + 3) / 4, B), dim3(4 * DD), 0, stream,
+                           lean_meta, part_m, part_l, part_o, ob, B, Hq, part_stride);
+      else
+        hipLaunchKernelGGL((decode_lean_reduce_kernel<DD, 1>), dim3(Hq, B), dim3(DD), 0, stream, lean_meta, part_m,
+                           part_l, part_o, ob, B, Hq, part_stride);
+      return;
+    }
+    auto launch = [&](auto kernel, dim3 grid) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, qb, ctx_lens, block_tables, kc, vc, ob, part_m, part_l,
+                         part_o, sl2, Hq, Hkv, max_blocks, pb, nparts, part_stride);
+    };
+    if (head_fast) launch(decode_kernel<DD, true>, dim3(Hkv, B, nparts));
+    else launch(decode_kernel<DD, false>, dim3(B, nparts, Hkv));
+    if (nparts > 1)
+      hipLaunchKernelGGL(decode_reduce_kernel<DD>, dim3(Hq, B), dim3(DD), 0, stream, ctx_lens, part_m, part_l, part_o,
+                         ob, Hq, pb, nparts, part_stride);
+  };
+  if (D == 128) run(std::integral_constant<int, 128>{});
+  else run(std::integral_constant<int, 64>{});
   PENNY_RETURN_LAUNCH();
 }

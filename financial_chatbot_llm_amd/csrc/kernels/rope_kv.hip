@@ -135,69 +135,37 @@ __global__ void rope_kv_fp8_kernel(const bf16* __restrict__ qkv, const int* __re
                                        P, S, T, inv_scale);
 }
 
+// fp8: the caches are e4m3 -- head dim 128 and inv_scale [2, Hkv] f32 required (see rope_kv_body F8)
 template <bool SLAB>
 static int launch_rope_kv(const void* qkv, const float* P, int S, const int* positions, const float* cos_sin,
-                          const int* slots, void* q_out, void* k_cache, void* v_cache, int T, int Hq, int Hkv, int D,
-                          int apply_rope, hipStream_t stream) {
+                          const int* slots, void* q_out, void* k_cache, void* v_cache, const float* inv_scale,
+                          int fp8, int T, int Hq, int Hkv, int D, int apply_rope, hipStream_t stream) {
   if (T <= 0) return 0;
-  const int threads = 256;
+  if (fp8 ? (D != 128 || !inv_scale) : (D != 128 && D != 64)) return (int)hipErrorInvalidValue;
   const dim3 grid(T, T <= 512 ? 2 : 1);
-  if (D == 128) {
-    hipLaunchKernelGGL((rope_kv_kernel<128, SLAB>), grid, dim3(threads), 0, stream, (const bf16*)qkv, positions,
-                       cos_sin, slots, (bf16*)q_out, (bf16*)k_cache, (bf16*)v_cache, Hq, Hkv, apply_rope, P, S, T);
-  } else if (D == 64) {
-    hipLaunchKernelGGL((rope_kv_kernel<64, SLAB>), grid, dim3(threads), 0, stream, (const bf16*)qkv, positions,
-                       cos_sin, slots, (bf16*)q_out, (bf16*)k_cache, (bf16*)v_cache, Hq, Hkv, apply_rope, P, S, T);
-  } else {
-    return (int)hipErrorInvalidValue;
+  auto launch = [&](auto kernel, auto... extra) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const bf16*)qkv, positions, cos_sin, slots, (bf16*)q_out,
+                       (bf16*)k_cache, (bf16*)v_cache, Hq, Hkv, apply_rope, P, S, T, extra...);
+  };
+  if (fp8) launch(rope_kv_fp8_kernel<SLAB>, inv_scale);
+  else if (D == 128) launch(rope_kv_kernel<128, SLAB, false>);
+  else launch(rope_kv_kernel<64, SLAB, false>);
+  PENNY_RETURN_LAUNCH();
+}
+
+// The activation is qkv [T, (Hq + 2*Hkv) * D] bf16 or, with P non-null, the S >= 1 split-K slabs
+// P [S, T, (Hq + 2*Hkv) * D] f32 of the QKV GEMM.  fp8 != 0: e4m3 caches, written with inv_scale.
+PENNY_API int penny_rope_kv_write(const void* qkv, const void* P, int S, const int* positions, const float* cos_sin,
+                                  const int* slots, void* q_out, void* k_cache, void* v_cache,
+                                  const float* inv_scale, int fp8, int T, int Hq, int Hkv, int D, int apply_rope,
+                                  hipStream_t stream) {
+  if (P != nullptr) {
+    if (S < 1) return (int)hipErrorInvalidValue;
+    return launch_rope_kv<true>(nullptr, (const float*)P, S, positions, cos_sin, slots, q_out, k_cache, v_cache,
+                                inv_scale, fp8, T, Hq, Hkv, D, apply_rope, stream);
   }
-  PENNY_RETURN_LAUNCH();
-}
-
-// fp8 (e4m3) caches, head dim 128: inv_scale [2, Hkv] f32 (see rope_kv_kernel F8)
-template <bool SLAB>
-static int launch_rope_kv_fp8(const void* qkv, const float* P, int S, const int* positions, const float* cos_sin,
-                              const int* slots, void* q_out, void* k_cache, void* v_cache, const float* inv_scale,
-                              int T, int Hq, int Hkv, int D, int apply_rope, hipStream_t stream) {
-  if (T <= 0) return 0;
-  if (D != 128 || !inv_scale) return (int)hipErrorInvalidValue;
-  const dim3 grid(T, T <= 512 ? 2 : 1);
-  hipLaunchKernelGGL(rope_kv_fp8_kernel<SLAB>, grid, dim3(256), 0, stream, (const bf16*)qkv, positions,
-                     cos_sin, slots, (bf16*)q_out, (bf16*)k_cache, (bf16*)v_cache, Hq, Hkv, apply_rope, P, S, T,
-                     inv_scale);
-  PENNY_RETURN_LAUNCH();
-}
-
-PENNY_API int penny_rope_kv_write_fp8(const void* qkv, const int* positions, const float* cos_sin, const int* slots,
-                                      void* q_out, void* k_cache, void* v_cache, const float* inv_scale, int T,
-                                      int Hq, int Hkv, int D, int apply_rope, hipStream_t stream) {
-  return launch_rope_kv_fp8<false>(qkv, nullptr, 0, positions, cos_sin, slots, q_out, k_cache, v_cache, inv_scale, T,
-                                   Hq, Hkv, D, apply_rope, stream);
-}
-
-PENNY_API int penny_rope_kv_write_slabs_fp8(const void* P, int S, const int* positions, const float* cos_sin,
-                                            const int* slots, void* q_out, void* k_cache, void* v_cache,
-                                            const float* inv_scale, int T, int Hq, int Hkv, int D, int apply_rope,
-                                            hipStream_t stream) {
-  if (S < 1) return (int)hipErrorInvalidValue;
-  return launch_rope_kv_fp8<true>(nullptr, (const float*)P, S, positions, cos_sin, slots, q_out, k_cache, v_cache,
-                                  inv_scale, T, Hq, Hkv, D, apply_rope, stream);
-}
-
-PENNY_API int penny_rope_kv_write(const void* qkv, const int* positions, const float* cos_sin, const int* slots,
-                                  void* q_out, void* k_cache, void* v_cache, int T, int Hq, int Hkv, int D,
-                                  int apply_rope, hipStream_t stream) {
-  return launch_rope_kv<false>(qkv, nullptr, 0, positions, cos_sin, slots, q_out, k_cache, v_cache, T, Hq, Hkv, D,
-                               apply_rope, stream);
-}
-
-// qkv given as the S split-K slabs P [S, T, (Hq + 2*Hkv) * D] f32 of the QKV GEMM
-PENNY_API int penny_rope_kv_write_slabs(const void* P, int S, const int* positions, const float* cos_sin,
-                                        const int* slots, void* q_out, void* k_cache, void* v_cache, int T, int Hq,
-                                        int Hkv, int D, int apply_rope, hipStream_t stream) {
-  if (S < 1) return (int)hipErrorInvalidValue;
-  return launch_rope_kv<true>(nullptr, (const float*)P, S, positions, cos_sin, slots, q_out, k_cache, v_cache, T, Hq,
-                              Hkv, D, apply_rope, stream);
+  return launch_rope_kv<false>(qkv, nullptr, 0, positions, cos_sin, slots, q_out, k_cache, v_cache, inv_scale, fp8, T,
+                               Hq, Hkv, D, apply_rope, stream);
 }
 
 // Context-parallel form: rotated q and k heads of qkv [T, (Hq + 2*Hkv) * D] -> qk [T, Hq + Hkv, D]

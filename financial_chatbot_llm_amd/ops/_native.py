@@ -54,26 +54,15 @@ _SIGS = {
     "penny_gelu": [P, c_long, P],
     "penny_embedding": [P, P, P, c_int, c_int, c_int, c_int, P],
     "penny_rope_qk": [P, P, P, P, c_int, c_int, c_int, c_int, P],
-    "penny_rope_kv_write": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
-    "penny_rope_kv_write_slabs": [P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
-    "penny_rope_kv_write_fp8": [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
-    "penny_rope_kv_write_slabs_fp8": [P, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "penny_rope_kv_write": [P, P, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "penny_kv_dequant_fp8": [P, P, P, c_long, c_int, c_int, P],
-    "penny_attention_decode_fp8": [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                   c_float, c_int, P, c_int, c_int, P, P],
-    "penny_attention_prefill_fp8": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P,
-                                    P, c_int, P, P],
-    "penny_attention_prefill_lean_fp8": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, P,
-                                         c_int, P, c_int, P, P, P, P],
     "penny_attention_prefill": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P,
-                                c_int, P],
+                                c_int, c_int, P, c_int, P, P, P, P],
     "penny_attention_prefill_variant": [c_int],
     "penny_gemm_prefill_set_group": [c_int],
-    "penny_attention_prefill_lean": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, P, c_int, P,
-                                     c_int, P, P, P],
     "penny_splitk_reduce_silu": [P, c_int, c_int, c_int, P, c_int, P],
     "penny_attention_decode": [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                               c_float, c_int, P, c_int, c_int, P],
+                               c_float, c_int, P, c_int, c_int, P, c_int, P],
     "penny_sample": [P, c_int, c_long, P, P, P, P, P, P, c_int, c_int, P],
     "penny_sample_fsm": [P, c_int, c_long, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, c_int, P,
                          c_int, P],

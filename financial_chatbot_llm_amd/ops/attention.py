@@ -216,36 +216,22 @@ def rope_kv_write(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: Optional[
     """Rotate q/k of a fused QKV activation, write k/v into the paged cache, return q [T,Hq,D].
     ``qkv`` may be the unreduced :class:`~.gemm.Slabs` of the split-K QKV GEMM (summed here).
     fp8 cache: K after RoPE (f32, no bf16 rounding in between) and V are quantised with
-    ``kv_scales.inv`` (``penny_rope_kv_write_fp8`` / ``_slabs_fp8``)."""
+    ``kv_scales.inv``."""
     fp8 = is_fp8(k_cache)
     if fp8 and D != 128:
         raise ValueError(f"fp8 KV cache needs head dim 128, got {D}")
-    if isinstance(qkv, Slabs):
-        S, T, _ = qkv.P.shape
-        if N.use_native(qkv.P):
-            q = torch.empty((T, Hq, D), dtype=torch.bfloat16, device=qkv.P.device)
-            if fp8:
-                inv = (kv_scales or _unit_scales(Hkv, q.device)).inv
-                N.call("penny_rope_kv_write_slabs_fp8", N.ptr(qkv.P), S, N.ptr(positions),
-                       N.ptr(cos_sin) if apply_rope else None, N.ptr(slots), N.ptr(q), N.ptr(k_cache),
-                       N.ptr(v_cache), N.ptr(inv), T, Hq, Hkv, D, int(apply_rope), N.stream())
-                return q
-            N.call("penny_rope_kv_write_slabs", N.ptr(qkv.P), S, N.ptr(positions),
-                   N.ptr(cos_sin) if apply_rope else None, N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache),
-                   T, Hq, Hkv, D, int(apply_rope), N.stream())
-            return q
-        qkv = qkv.materialize()
-    T = qkv.shape[0]
-    if N.use_native(qkv):
-        q = torch.empty((T, Hq, D), dtype=qkv.dtype, device=qkv.device)
-        if fp8:
-            inv = (kv_scales or _unit_scales(Hkv, q.device)).inv
-            N.call("penny_rope_kv_write_fp8", N.ptr(qkv), N.ptr(positions), N.ptr(cos_sin) if apply_rope else None,
-                   N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache), N.ptr(inv), T, Hq, Hkv, D,
-                   int(apply_rope), N.stream())
-            return q
-        N.call("penny_rope_kv_write", N.ptr(qkv), N.ptr(positions), N.ptr(cos_sin) if apply_rope else None,
-               N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache), T, Hq, Hkv, D, int(apply_rope), N.stream())
+    slabs = qkv.P if isinstance(qkv, Slabs) else None
+    if slabs is not None and not N.use_native(slabs):
+        qkv, slabs = qkv.materialize(), None
+    src = qkv if slabs is None else slabs
+    T = src.shape[-2]
+    if N.use_native(src):
+        q = torch.empty((T, Hq, D), dtype=torch.bfloat16 if slabs is not None else qkv.dtype, device=src.device)
+        inv = (kv_scales or _unit_scales(Hkv, q.device)).inv if fp8 else None
+        N.call("penny_rope_kv_write", N.ptr(qkv) if slabs is None else None, N.ptr(slabs),
+               slabs.shape[0] if slabs is not None else 0, N.ptr(positions), N.ptr(cos_sin) if apply_rope else None,
+               N.ptr(slots), N.ptr(q), N.ptr(k_cache), N.ptr(v_cache), N.ptr(inv), int(fp8), T, Hq, Hkv, D,
+               int(apply_rope), N.stream())
         return q
     x = qkv.view(T, Hq + 2 * Hkv, D)
     q, k, v = x[:, :Hq], x[:, Hq:Hq + Hkv], x[:, Hq + Hkv:]
@@ -511,7 +497,7 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
             raise ValueError("fp8 KV cache: prescaled q is not supported")
         if D != 128:
             raise ValueError(f"fp8 KV cache needs head dim 128, got {D}")
-    flags = int(causal) | (2 if q_prescaled else 0)
+    flags = int(causal) | (2 if q_prescaled else 0) | (4 if fp8 else 0)    # penny_attention_prefill flags
     Hkv = k_cache.shape[1]
     S = block_tables.shape[0]
     assert k_cache.shape[-1] == KV_BS * D
@@ -521,31 +507,18 @@ def prefill(q: torch.Tensor, cu_q: torch.Tensor, ctx_lens: torch.Tensor, block_t
             # lean work list (prefill_lean_list): the counts ride along host-side as ``lean``
             ni, nm, nslots = lean if lean is not None else (int(work[0, 1]), int(work[0, 2]), int(work[0, 3]))
             po, pml = _lean_workspace(q.device, max(nslots, 1), Hkv, D)
-            if fp8:
-                N.call("penny_attention_prefill_lean_fp8", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens),
-                       N.ptr(block_tables), N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), Hq, Hkv, D,
-                       block_tables.shape[1], float(scale), flags, N.ptr(lse) if lse is not None else None,
-                       N.ptr(work[1:]), int(ni), N.ptr(work[1 + ni:]) if nm else None, int(nm), N.ptr(po), N.ptr(pml),
-                       N.ptr(kv_scales.scale) if kv_scales is not None else None, N.stream())
-                return out
-            N.call("penny_attention_prefill_lean", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens), N.ptr(block_tables),
-                   N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), Hq, Hkv, D, block_tables.shape[1], float(scale),
-                   flags, N.ptr(lse) if lse is not None else None, N.ptr(work[1:]), int(ni),
-                   N.ptr(work[1 + ni:]) if nm else None, int(nm), N.ptr(po), N.ptr(pml), N.stream())
-            return out
-        if max_q_len is None:
-            max_q_len = int((cu_q[1:] - cu_q[:-1]).max().item())
-        if fp8:
-            N.call("penny_attention_prefill_fp8", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens), N.ptr(block_tables),
-                   N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), S, int(max_q_len), Hq, Hkv, D, block_tables.shape[1],
-                   float(scale), flags, N.ptr(lse) if lse is not None else None,
-                   N.ptr(work) if work is not None else None, int(work.shape[0]) if work is not None else 0,
-                   N.ptr(kv_scales.scale) if kv_scales is not None else None, N.stream())
-            return out
+            # items, then merges; max_q_len is not read
+            wargs = (N.ptr(work[1:]), int(ni), 6, N.ptr(work[1 + ni:]) if nm else None, int(nm), N.ptr(po), N.ptr(pml))
+            max_q_len = 0
+        else:
+            if max_q_len is None:
+                max_q_len = int((cu_q[1:] - cu_q[:-1]).max().item())
+            wargs = ((N.ptr(work), int(work.shape[0]), 2, None, 0, None, None) if work is not None
+                     else (None, 0, 0, None, 0, None, None))      # LPT (sequence, tile) pairs, or the full grid
         N.call("penny_attention_prefill", N.ptr(q), N.ptr(cu_q), N.ptr(ctx_lens), N.ptr(block_tables),
                N.ptr(k_cache), N.ptr(v_cache), N.ptr(out), S, int(max_q_len), Hq, Hkv, D, block_tables.shape[1],
-               float(scale), flags, N.ptr(lse) if lse is not None else None,
-               N.ptr(work) if work is not None else None, int(work.shape[0]) if work is not None else 0, N.stream())
+               float(scale), flags, N.ptr(lse) if lse is not None else None, *wargs,
+               N.ptr(kv_scales.scale) if kv_scales is not None else None, N.stream())
         return out
     out = torch.empty_like(q) if out is None else out
     cu = cu_q.tolist()
@@ -728,24 +701,17 @@ def decode(q: torch.Tensor, ctx_lens: torch.Tensor, block_tables: torch.Tensor, 
         ws = workspace
         lean = (DECODE_LEAN and B >= LEAN_MIN_B and ws.lean_meta is not None
                 and ws.lean_meta.numel() >= LEAN_META0 + B + 2)
-        if fp8:
-            if not lean:
-                raise RuntimeError("fp8 KV cache: decode attention needs the lean kernel (PENNY_DECODE_LEAN=1, "
-                                   "PENNY_DECODE_LEAN_MIN_B <= batch, and a workspace with lean_meta)")
-            N.call("penny_attention_decode_fp8", N.ptr(q), N.ptr(ctx_lens), N.ptr(block_tables), N.ptr(k_cache),
-                   N.ptr(v_cache), N.ptr(out), N.ptr(ws.part_m), N.ptr(ws.part_l), N.ptr(ws.part_o), B, Hq, Hkv, D,
-                   block_tables.shape[1], ws.nparts, ws.part_stride, float(scale), _lean_grid(q.device, Hkv),
-                   N.ptr(ws.lean_meta), LEAN_MIN_PER_WAVE, LEAN_FLAGS if B >= LEAN_NT_MIN_B else LEAN_FLAGS & ~1,
-                   N.ptr(kv_scales.scale) if kv_scales is not None else None,
-                   N.stream() if stream is None else stream)
-            return out
+        if fp8 and not lean:
+            raise RuntimeError("fp8 KV cache: decode attention needs the lean kernel (PENNY_DECODE_LEAN=1, "
+                               "PENNY_DECODE_LEAN_MIN_B <= batch, and a workspace with lean_meta)")
         pb, nparts = ws.partitioning(B) if not lean else (ws.pb, ws.nparts)
-        args = [N.ptr(q), N.ptr(ctx_lens), N.ptr(block_tables), N.ptr(k_cache), N.ptr(v_cache), N.ptr(out),
-                N.ptr(ws.part_m), N.ptr(ws.part_l), N.ptr(ws.part_o), B, Hq, Hkv, D, block_tables.shape[1], pb,
-                nparts, ws.part_stride, float(scale)]
         lean_args = ((_lean_grid(q.device, Hkv), N.ptr(ws.lean_meta), LEAN_MIN_PER_WAVE,
                       LEAN_FLAGS if B >= LEAN_NT_MIN_B else LEAN_FLAGS & ~1) if lean else (0, None, 1, 0))
-        N.call("penny_attention_decode", *args, *lean_args, N.stream() if stream is None else stream)
+        N.call("penny_attention_decode", N.ptr(q), N.ptr(ctx_lens), N.ptr(block_tables), N.ptr(k_cache),
+               N.ptr(v_cache), N.ptr(out), N.ptr(ws.part_m), N.ptr(ws.part_l), N.ptr(ws.part_o), B, Hq, Hkv, D,
+               block_tables.shape[1], pb, nparts, ws.part_stride, float(scale), *lean_args,
+               N.ptr(kv_scales.scale) if kv_scales is not None else None, int(fp8),
+               N.stream() if stream is None else stream)
         return out
     out = torch.empty_like(q) if out is None else out
     ctx = ctx_lens.tolist()

@@ -269,11 +269,12 @@ def test_prefill_non_causal_errors(prefill_cache):
     bt = torch.zeros((1, 1), dtype=torch.int32, device=DEV)
     with pytest.raises(ValueError, match="causal"):
         ops.prefill(q, cu, ctx, bt, kcd, vcd, SCALE, causal=False, max_q_len=5)
-    # the launcher refuses it too
+    # the launcher refuses it too (flags: bit 2 = e4m3 cache, bit 0 = causal left clear)
     from financial_chatbot_llm_amd.ops import _native as N
     out = torch.empty_like(q)
-    rc = N.load().penny_attention_prefill_fp8(N.ptr(q), N.ptr(cu), N.ptr(ctx), N.ptr(bt), N.ptr(kcd), N.ptr(vcd),
-                                              N.ptr(out), 1, 5, 8, HKV, D, 1, SCALE, 0, None, None, 0, None, N.stream())
+    rc = N.load().penny_attention_prefill(N.ptr(q), N.ptr(cu), N.ptr(ctx), N.ptr(bt), N.ptr(kcd), N.ptr(vcd),
+                                          N.ptr(out), 1, 5, 8, HKV, D, 1, SCALE, 4, None, None, 0, 0, None, 0, None, None,
+                                          None, N.stream())
     assert rc != 0
 
 
